@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- batched CRDT merge throughput on MI355X (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
 
 Default workload = BASELINE.json configs[4] (the north_star's scaling
 config): a 100M-replica x 64-node uint64 G-Counter population sharded by
@@ -16,10 +16,18 @@ N>1: one process per GPU.  Under torchrun the ranks come from the env; a
 plain `python bench.py --gpus N` spawns its own N rank processes before the
 parent touches the GPU and exits with their status.
 
-Prints ONE JSON line (rank 0) with value = whole-job units/s, a roofline
-object for the dominant kernel (HIP-event-timed on the launch stream) and a
-cpu_baseline object (the oracle restatement on this host's cores, rank 0 at
-N=1 only, bounded sample).
+Prints ONE JSON line (rank 0) with value = whole-job units/s, ms_per_step and
+a roofline object for the dominant kernel (HIP-event-timed on the launch
+stream).  A plain run does only that: set up, warm up, time the K steps, print.
+
+--dump-outputs DIR: after the timed steps, what the last step computed (the
+arrays its caller receives) goes to DIR/<name>.npy (dump_outputs below).
+
+--full adds the measurements that take runs of their own: the self-measured
+streaming peaks (roofline.measured_peak), the PCIe-inclusive e2e_pcie time and
+the cpu_baseline object (the oracle restatement on this host's cores, rank 0
+at N=1 only, bounded sample, with its parity spot-check of the device
+outputs).  --no-peaks / --no-e2e / --no-cpu-baseline drop one of them.
 """
 from __future__ import annotations
 
@@ -209,9 +217,70 @@ def sum_over_ranks(x: int, world: int, dev) -> int:
     return int(t.item())
 
 
+DUMP_MAX_BYTES = 64_000_000   # --dump-outputs: bound on the float forms of all arrays together
+DUMP_SEED = 2024
+
+
+def dump_outputs(outdir, arrays, prefix=""):
+    """--dump-outputs: every array of `arrays` (name -> tensor or ndarray) as
+    outdir/<prefix><name>.npy.  The outputs are integers, so each is stored
+    in a float form that holds them exactly: 8-byte integers as float64
+    [..., 2] = (high, low) 32-bit halves of the bit pattern, 4-byte integers
+    as float64, narrower ones as float32.  When the float forms exceed
+    DUMP_MAX_BYTES together, every array keeps the same fraction of its rows
+    (first axis): a sorted sample drawn from DUMP_SEED, the same rows for
+    arrays of the same length, so runs with the same arguments store the
+    same elements."""
+    os.makedirs(outdir, exist_ok=True)
+    form = lambda x: 16 if x.element_size() == 8 else 8 if x.element_size() == 4 else 4
+    arrays = {k: (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))) for k, v in arrays.items()}
+    total = sum(v.numel() * form(v) for v in arrays.values())
+    frac = min(1.0, (DUMP_MAX_BYTES - 1024 * len(arrays)) / max(total, 1))
+    rng, picks = np.random.default_rng(DUMP_SEED), {}
+    for name, x in arrays.items():
+        rows = x.shape[0] if x.dim() else 1
+        if frac < 1.0 and rows > 1:
+            if rows not in picks:
+                picks[rows] = torch.from_numpy(np.sort(rng.choice(rows, max(1, int(rows * frac)), replace=False)))
+            x = x[picks[rows].to(x.device)]
+        a = x.detach().cpu().contiguous().numpy()
+        if a.dtype.kind == "f":
+            f = a.astype(np.float64 if a.itemsize == 8 else np.float32)
+        elif a.itemsize == 8:
+            u = a.view(np.uint64)
+            f = np.stack([(u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], -1)
+        else:
+            f = a.astype(np.float64 if a.itemsize == 4 else np.float32)
+        np.save(os.path.join(outdir, f"{prefix}{name}.npy"), f)
+
+
+def _tuple_arrays(t, prefix=""):
+    return {prefix + "key": t.key, prefix + "ts": t.ts, prefix + "rep": t.rep, prefix + "tomb": t.tomb}
+
+
+def _refmerge_arrays(o):
+    """A refmerge output's defined part: the new Diffs up to off[-1], a
+    slot's string id only where it holds a string, its sum only where it
+    holds a sum (the rest of those buffers is never written)."""
+    n = int(o["off"][-1].item())
+    kind = o["st_kind"]
+    return {"off": o["off"], "ts": o["ts"][:n], "origin": o["origin"][:n], "src": o["src"][:n], "st_kind": kind,
+            "st_str": torch.where(kind == 1, o["st_str"], torch.zeros_like(o["st_str"])),
+            "st_sum": torch.where(kind == 2, o["st_sum"], torch.zeros_like(o["st_sum"]))}
+
+
+def _population_arrays(h, prefix=""):
+    """NativePopulation.read() with the undefined state fields zeroed (as _refmerge_arrays)."""
+    h = dict(h)
+    h["st_str"] = np.where(h["st_kind"] == 1, h["st_str"], 0).astype(np.uint32)
+    h["st_sum"] = np.where(h["st_kind"] == 2, h["st_sum"], 0).astype(np.int64)
+    return {prefix + k: v for k, v in h.items()}
+
+
 # --------------------------------------------------------------------------- workloads
 class Workload:
-    """setup() allocates device inputs; step() enqueues one pass of the hot path."""
+    """setup() allocates device inputs; step() enqueues one pass of the hot path;
+    outputs() names the arrays the last step's caller received (--dump-outputs)."""
     name = ""
     unit = "replica-merges/s"
     dtype = "u64"
@@ -221,6 +290,7 @@ class Workload:
     def units(self) -> int: ...
     def bytes_per_launch(self) -> int: ...
     def step(self): ...
+    def outputs(self) -> dict: ...
 
 
 class GCounterJoin(Workload):
@@ -248,6 +318,9 @@ class GCounterJoin(Workload):
 
     def io(self):
         return [self.a, self.b], [self.out]
+
+    def outputs(self):
+        return {"out": self.out}
 
     def cpu_baseline(self, seconds, threads):
         from oracle import oracle
@@ -288,6 +361,9 @@ class PNCounterJoin(GCounterJoin):
     def io(self):
         return [self.a, self.na, self.b, self.nb], [self.out, self.nout]
 
+    def outputs(self):
+        return {"p_out": self.out, "n_out": self.nout}
+
     def cpu_baseline(self, seconds, threads):
         return None
 
@@ -316,6 +392,9 @@ class VClockClassify(Workload):
 
     def io(self):
         return [self.a, self.b], [self.cls]
+
+    def outputs(self):
+        return {"cls": self.cls}
 
     def cpu_baseline(self, seconds, threads):
         from oracle import oracle
@@ -369,6 +448,9 @@ class SetMerge(Workload):
         o = self.out.slice(self.n_out)
         ins = [t for side in self._sides() for t in (side.key, side.ts, side.rep, side.tomb)]
         return ins, [o.key, o.ts, o.rep, o.tomb, self.count]
+
+    def outputs(self):
+        return dict(_tuple_arrays(self.out.slice(int(self.count.item()))), count=self.count)
 
     def cpu_baseline(self, seconds, threads):
         """The oracle's serial merge run on `threads` host threads, each over
@@ -535,6 +617,9 @@ class ShardFold(Workload):
             if self.world > 1:
                 shard.allreduce_max_u64(self.fold, self.eng)
 
+    def outputs(self):
+        return {"fold": self.fold}
+
     def e2e_stream(self, chunk_bytes=1 << 30):
         """VERDICT r05 missing #4: the PCIe-inclusive time of the whole
         configs[4] population.  It streams from pinned host memory into HBM
@@ -660,6 +745,10 @@ class ShardSetMerge(SetMerge):
                                               outs=[self.gout])[0]
         self.last_count = None
 
+    def outputs(self):
+        n = len(self.last) if self.last_count is None else int(self.last_count.item())
+        return dict(_tuple_arrays(self.last.slice(n)), count=np.array([n], np.int64))
+
     def extra(self, avg_ms):
         return {"exchange": {"n_out_total": self.n_total, "ranks": self.world,
                              "note": "N>1: each rank sends every tuple to its key-range owner and receives the "
@@ -715,6 +804,12 @@ class LoopbackSetMerge(Workload):
     def step(self):
         self.last = self.comm.set_merge_local(self.A, self.B, lww=self.lww, gather=True, cap=self.cap,
                                               outs=self.outs)
+
+    def outputs(self):
+        out = {}
+        for r, t in enumerate(self.last):            # every rank's copy of the merged state
+            out.update(_tuple_arrays(t, f"r{r}_"))
+        return out
 
     def extra(self, avg_ms):
         return {"exchange": {"transport": "loopback", "ranks": self.R, "n_out_total": self.n_out,
@@ -779,6 +874,16 @@ class LoopbackGossipRound(Workload):
         for p in self.pops:
             p.undo()
 
+    def outputs(self):
+        """Every step is the same round, undone after: the round once more,
+        every rank's population read before it is undone."""
+        self.gossip.NativePopulation.round_sharded(self.comm, self.pops, self.peers)
+        out = {}
+        for r, p in enumerate(self.pops):
+            out.update(_population_arrays(p.read(), f"r{r}_"))
+            p.undo()
+        return out
+
     def extra(self, avg_ms):
         return {"exchange": {"transport": "loopback", "ranks": self.R,
                              "note": "the pulled Diffs of other ranks' replicas move as device copies on the one "
@@ -826,6 +931,9 @@ class ShardJoin(Workload):
             dist.all_reduce(self.buf, op=dist.ReduceOp.MAX)
         self.eng.ordered_i64_to_u64(self.buf, out=self.state)
 
+    def outputs(self):
+        return {"state": self.state}
+
     def extra(self, avg_ms):
         S = self.rows * self.nodes * 8
         g = self.world
@@ -870,6 +978,9 @@ class RefMergeBatch(Workload):
 
     def step(self):
         self.last = self.eng.refmerge_batch(self.dev)
+
+    def outputs(self):
+        return _refmerge_arrays(self.last)
 
     def io(self):
         o, n, ns = self.last, self.n_out, int(self.host["n_slots"])
@@ -975,7 +1086,10 @@ class RefMergeDelta(RefMergeBatch):
 
     def step(self):
         self.buf.copy_(self.buf0)
-        self.eng.refmerge_delta(self.dev, self.st)
+        self.last = self.eng.refmerge_delta(self.dev, self.st)
+
+    def outputs(self):
+        return dict(_refmerge_arrays(self.last), **{"state_" + k: v for k, v in self.st.items()})
 
     def cpu_baseline(self, seconds, threads):
         return None
@@ -1048,7 +1162,21 @@ class GossipRound(Workload):
             self.pop.undo()
             return None
         self.pop.restore(self.init)
-        return self.pop.round(self.peers)
+        self.last = self.pop.round(self.peers)
+        return self.last
+
+    def _round(self):
+        self.pop.round(self.peers)
+
+    def outputs(self):
+        """Native: every step is the same round, undone after, so the round
+        runs once more and the population is read before it is undone."""
+        if not self.native:
+            return _refmerge_arrays(self.last)
+        self._round()
+        out = _population_arrays(self.pop.read())
+        self.pop.undo()
+        return out
 
     def cpu_baseline(self, seconds, threads):
         """The round's merge on the host: oc_refmerge (C restatement of
@@ -1163,7 +1291,11 @@ class GossipRoundWire(GossipRound):
             return None
         self.pop.restore(self.init)
         self.pop.str_bytes, self.pop.str_off = self.str0
-        return self.pop.round_wire(self.data, self.body_off.tolist(), self.keys, self.vals, self.n_e, self.n_p)
+        self.last = self.pop.round_wire(self.data, self.body_off.tolist(), self.keys, self.vals, self.n_e, self.n_p)
+        return self.last
+
+    def _round(self):
+        self.pop.round_wire(self.data, self.body_off, self.keys, self.vals)
 
 
 class ServerMerge(Workload):
@@ -1226,6 +1358,17 @@ class ServerMerge(Workload):
         for s, body in zip(self.srv, self.bodies):
             assert s.IngestBinary(body) == 0
         self.server.merge_servers(self.srv)
+
+    def outputs(self):
+        """Each server's Diff (ts, local origin) and its CurrentState as the bytes of its sorted "key=value" lines."""
+        out = {}
+        for p, s in enumerate(self.srv):
+            sig = s.DiffSignature
+            out[f"s{p}_diff_ts"] = np.array([t for t, _ in sig], np.int64)
+            out[f"s{p}_diff_local"] = np.array([o == "local" for _, o in sig], np.uint8)
+            state = "".join(f"{k}={v}\n" for k, v in sorted(s.CurrentState.items()))
+            out[f"s{p}_state"] = np.frombuffer(state.encode("utf-8", "surrogatepass"), np.uint8)
+        return out
 
     def cpu_baseline(self, seconds, threads):
         """oc_refmerge of each replica's (Diff, pulled RemoteDiff), one replica
@@ -1330,11 +1473,16 @@ def main():
     ap.add_argument("--entries", type=int, default=10_000)
     ap.add_argument("--demo-replicas", type=int, default=5)      # main.go:319-321
     ap.add_argument("--demo-entries", type=int, default=10_000)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the streaming peaks, the PCIe-inclusive e2e_pcie time and the CPU baseline "
+                         "(with its parity spot-check); a plain run only times the steps")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive e2e_pcie measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the PCIe-inclusive e2e_pcie measurement")
     ap.add_argument("--no-peaks", action="store_true",
-                    help="skip the self-measured peak sweep (timeline traces: the trace then ends with the timed loop)")
+                    help="with --full: skip the self-measured peak sweep")
     ap.add_argument("--option", action="append", default=[],
                     help="name=value kernel knob (crdt_set_option; loads the diagnostic build, A/B runs only)")
     args = ap.parse_args()
@@ -1396,26 +1544,34 @@ def main():
     total_units = sum_over_ranks(wl.units() * args.steps, world, dev)
     value = total_units / elapsed
 
+    if args.dump_outputs:                             # before --full's legs run the step again
+        dump_outputs(args.dump_outputs, wl.outputs(), f"rank{rank}_" if world > 1 else "")
+
     out = None
     if rank == 0:
         avg_ms = float(np.mean(step_ms))
         med_ms = float(np.median(step_ms))
         achieved = wl.bytes_per_launch() / (avg_ms / 1e3) / 1e9
         traffic = load_traffic(wl)
-        peaks = measure_peaks(eng) if not args.no_peaks else {"copy": float("nan"), "read": float("nan"),
-                                                               "skipped": "--no-peaks"}
+        if not args.full:
+            peaks = None
+        elif args.no_peaks:
+            peaks = {"copy": float("nan"), "read": float("nan"), "skipped": "--no-peaks"}
+        else:
+            peaks = measure_peaks(eng)
         roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                "measured_peak": peaks, "frac_of_copy_peak": round(achieved / peaks["copy"], 4),
-                "frac_of_read_peak": round(achieved / peaks["read"], 4),
+                "measured_peak": peaks or {"skipped": "measured with --full"},
+                "frac_of_copy_peak": round(achieved / peaks["copy"], 4) if peaks else None,
+                "frac_of_read_peak": round(achieved / peaks["read"], 4) if peaks else None,
                 "peak_basis": ("read (a read-dominated step: compare frac_of_read_peak)"
                                if getattr(wl, "read_dominated", False) else "copy (reads + writes)"),
                 "kernel": wl.kernel, "bytes_per_launch": wl.bytes_per_launch(),
                 "avg_launch_us": round(avg_ms * 1e3, 2), "median_launch_us": round(med_ms * 1e3, 2),
                 "timing": "HIP events on the launch stream, per step"}
-        e2e = measure_e2e(wl) if world == 1 and not args.no_e2e else None
+        e2e = measure_e2e(wl) if args.full and world == 1 and not args.no_e2e else None
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and hasattr(wl, "cpu_baseline"):
+        if args.full and world == 1 and not args.no_cpu_baseline and hasattr(wl, "cpu_baseline"):
             threads, aff = cpu_share()
             cpu = wl.cpu_baseline(args.cpu_seconds, threads)
             if cpu is not None:
