@@ -1,0 +1,481 @@
+// setread.hip -- the read side of the keyed sets: live elements, cardinality
+// and membership of a sorted LWW / OR-Set state.
+//
+// Semantics, pinned to the merges of sets.hip.  For tuples t[0 .. n) sorted
+// ascending by (key, ts, rep), copies of one tag in any order:
+//   OR-Set : a tag is live iff none of its copies is tombstoned; a key is a
+//            member iff it has a live tag.
+//   LWW    : a key is a member iff the FIRST copy of its maximal (ts, rep)
+//            tag has tomb == 0 (the winner rule of sets.hip).
+// elements(t) = the member keys, ascending, each once = the keys of
+// merge(t, {}) whose (OR-Set: any) output tuple has tomb == 0.
+//
+// GPU structure: a streaming job over tiles of 2048 tuples, one workgroup of
+// four waves each, every decision a wave64 ballot word -- the tile's logic
+// runs on 64-bit masks (same-key-as-next, same-tag-as-next, tomb), one mask
+// bit per tuple, a segmented OR per mask word being one 64-bit add.
+//   count : per tile the `emit` bitmap (bit set at the LAST tuple of a member
+//           key's run), the tile's member count and, OR-Set only, a carry
+//           record.  No tile waits for another: each evaluates with an empty
+//           carry; what a carry can change is one bit, the first key end.
+//   scan  : one workgroup.  A tile's record is the FUNCTION it applies to
+//           the carry state (tomb-OR of the open tag run, live-any of the
+//           open key run: 2 bits, so a 4-entry table) plus the 4 outcomes of
+//           its first key end; composing tables is associative, so the
+//           carries into all tiles are a prefix scan of compositions --
+//           linear however many tiles one key or tag spans.  It patches the
+//           at most one affected emit bit and count per tile, scans the
+//           counts to offsets and stores the total.
+//   write : (elements only) reads the keys and the bitmap, stores each
+//           emitting key at its rank.
+// LWW needs no carry: the last tuple of a key's run holds the key's maximal
+// tag, and the walk back over equal-tag copies to the first one's tomb goes
+// through global memory, as k_lww_write's does.
+//
+// The tuple count may stay on the device (n_dev): every kernel reads it,
+// tiles at or past min(*n_dev, n_max) do nothing, and *n_dev > n_max touches
+// no tuple, stores a count of ~0 and raises CRDT_DEV_RANGE.  No kernel reads
+// an index at or past that length or before 0.
+#include "scan.hpp"
+
+namespace crdt {
+
+constexpr int RT = 2048;                 // tuples per tile
+constexpr int RB = 256;                  // threads per tile (4 waves)
+constexpr int RWW = RT / RB;             // 64-tuple mask words per wave (consecutive: 512 tuples)
+constexpr int RNW = RT / 64;             // emit bitmap words per tile
+constexpr uint32_t kReadScanMax = 16384; // tiles per scan round (16 per thread)
+
+// ---- carry records.  State s = tor | live << 1 (tor: a tombstone seen in
+// the open tag run; live: a live tag closed in the open key run).  A record:
+//   bits 0-7   F: the state after the segment, 2 bits per state before it
+//   bits 8-11  E: whether the segment's first key end emits, per state before
+//   bit  12    the segment holds a key end
+//   bits 16-   its position in the segment
+constexpr uint32_t kRecId = 0xE4u;       // F = identity, no key end
+constexpr uint32_t kRecKE = 1u << 12;
+__device__ __forceinline__ uint32_t rec_f(uint32_t r, uint32_t s) { return (r >> (2 * s)) & 3u; }
+__device__ __forceinline__ uint32_t rec_e(uint32_t r, uint32_t s) { return (r >> (8 + s)) & 1u; }
+__device__ __forceinline__ uint32_t rec_pos(uint32_t r) { return r >> 16; }
+// segment a, then segment b (which starts off_b tuples after a's start)
+__device__ __forceinline__ uint32_t rec_then(uint32_t a, uint32_t b, uint32_t off_b) {
+    uint32_t f = 0, e = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 4; ++s) {
+        const uint32_t as = rec_f(a, s);
+        f |= rec_f(b, as) << (2 * s);
+        e |= rec_e(b, as) << (8 + s);
+    }
+    if (a & kRecKE) return f | (a & 0xffff1f00u);
+    if (b & kRecKE) return f | e | kRecKE | ((rec_pos(b) + off_b) << 16);
+    return f;
+}
+// F alone (the scan's operator)
+__device__ __forceinline__ uint32_t fn_then(uint32_t a, uint32_t b) {
+    uint32_t f = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 4; ++s) f |= rec_f(b, rec_f(a, s)) << (2 * s);
+    return f;
+}
+
+// One mask word of an OR-Set state: V valid tuples (low bits), ST / SK the
+// tuple has a successor with the same tag / key, TB its tomb, pt / pk the
+// word's first tuple continues the tag / key run before it.  *emit0 = the
+// emitting key ends under an empty carry.
+__device__ __forceinline__ uint32_t or_word_rec(uint64_t V, uint64_t ST, uint64_t SK, uint64_t TB, bool pt, bool pk,
+                                                uint64_t *emit0) {
+    *emit0 = 0;
+    if (V == 0) return kRecId;
+    const uint64_t TE = V & ~ST, KE = V & ~SK;           // tag run ends, key run ends (a subset)
+    // segmented any(): the carry of an add runs from a set bit up to its run's end bit and stops there
+    const uint64_t dead = TE & (((V & ~TE) + (TB & ~TE)) | TB);
+    const uint64_t LV = TE & ~dead;                      // live tags, at their ends
+    *emit0 = KE & (((V & ~KE) + (LV & ~KE)) | LV);
+    const bool any_te = TE != 0, any_ke = KE != 0;
+    const uint64_t f_te = TE & (0 - TE), f_ke = KE & (0 - KE);
+    const bool lead_tor = any_te ? (dead & f_te) != 0 : TB != 0;
+    const uint64_t up_k = any_ke ? (f_ke | (f_ke - 1)) : ~0ull;
+    const bool lead_rest = (LV & ~f_te & up_k) != 0;     // live tags of the leading key run but the first closing tag
+    bool trail_tor = false, trail_live = false;          // the open runs' state at the end
+    if (any_te) {
+        const uint64_t h = 1ull << (63 - __builtin_clzll(TE));
+        trail_tor = (TB & ~(h | (h - 1))) != 0;
+    }
+    if (any_ke) {
+        const uint64_t h = 1ull << (63 - __builtin_clzll(KE));
+        trail_live = (LV & ~(h | (h - 1))) != 0;
+    }
+    uint32_t r = any_ke ? (kRecKE | ((uint32_t)__builtin_ctzll(KE) << 16)) : 0u;
+#pragma unroll
+    for (uint32_t s = 0; s < 4; ++s) {
+        const bool tin = pt && (s & 1), lin = pk && (s & 2);
+        const bool first_live = any_te && !(tin || lead_tor);
+        const bool lead_live = lin || first_live || lead_rest;
+        const bool tor = any_te ? trail_tor : (tin || lead_tor);
+        const bool live = any_ke ? trail_live : lead_live;
+        r |= ((tor ? 1u : 0u) | (live ? 2u : 0u)) << (2 * s);
+        r |= (lead_live ? 1u : 0u) << (8 + s);
+    }
+    return r;
+}
+
+// the call's tuple count: n_max, or the device count when it is in range
+__device__ __forceinline__ bool read_len(uint64_t n_max, const uint64_t *__restrict__ n_dev, uint64_t *n) {
+    *n = n_dev ? *n_dev : n_max;
+    return *n <= n_max;
+}
+
+// ---------------------------------------------------------------- OR-Set count pass
+template <bool BITS>
+__global__ __launch_bounds__(RB) void k_or_read(crdt_tuples T, uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                                                uint32_t *__restrict__ tcnt, uint32_t *__restrict__ rec,
+                                                uint64_t *__restrict__ bits) {
+    __shared__ uint32_t s_rec[RB / 64], s_cnt[RB / 64];
+    uint64_t n;
+    if (!read_len(n_max, n_dev, &n)) return;
+    const uint64_t t = blockIdx.x, tb = t * RT;
+    if (tb >= n) return;                                 // (uniform; so n > 0 below)
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i0 = tb + (uint64_t)wv * (64 * RWW);
+    // every load up front, indices clamped into [0, n): nothing at or past n is read
+    uint64_t k[RWW], kn[RWW], ts[RWW], tn[RWW];
+    uint32_t r[RWW], rn[RWW];
+    uint8_t tm[RWW];
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+        const uint64_t a = i < n ? i : n - 1, b = i + 1 < n ? i + 1 : n - 1;
+        k[j] = T.key[a];
+        kn[j] = T.key[b];
+        ts[j] = T.ts[a];
+        tn[j] = T.ts[b];
+        r[j] = T.rep[a];
+        rn[j] = T.rep[b];
+        tm[j] = T.tomb[a];
+    }
+    // the tuple before the wave's first: does it open the wave's first runs?
+    bool pk0 = false, pt0 = false;
+    if (lane == 0 && i0 > 0 && i0 < n) {
+        pk0 = T.key[i0 - 1] == k[0];
+        pt0 = pk0 && T.ts[i0 - 1] == ts[0] && T.rep[i0 - 1] == r[0];
+    }
+    bool pk = __ballot(pk0) != 0, pt = __ballot(pt0) != 0;
+    uint32_t wr[RWW], agg = kRecId;
+    uint64_t e0[RWW];
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+        const bool v = i < n, sk = i + 1 < n && k[j] == kn[j];
+        const bool st = sk && ts[j] == tn[j] && r[j] == rn[j];
+        const uint64_t V = __ballot(v), SK = __ballot(sk), ST = __ballot(st), TB = __ballot(v && tm[j] != 0);
+        wr[j] = or_word_rec(V, ST, SK, TB, pt, pk, &e0[j]);
+        agg = rec_then(agg, wr[j], (uint32_t)j * 64);
+        pt = (ST >> 63) != 0;
+        pk = (SK >> 63) != 0;
+    }
+    if (lane == 0) s_rec[wv] = agg;
+    __syncthreads();
+    // the state the tile's earlier waves leave (under the tile's empty carry)
+    uint32_t pre = kRecId;
+    for (int w = 0; w < wv; ++w) pre = fn_then(pre, s_rec[w] & 0xffu);
+    uint32_t s = rec_f(pre, 0), cnt = 0;
+    uint64_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        uint64_t e = e0[j];
+        if ((wr[j] & kRecKE) && rec_e(wr[j], s) != rec_e(wr[j], 0)) e ^= 1ull << rec_pos(wr[j]);
+        s = rec_f(wr[j], s);
+        cnt += (uint32_t)__popcll(e);
+        if (lane == j) mine = e;
+    }
+    if (BITS && lane < RWW) bits[t * RNW + (uint64_t)wv * RWW + lane] = mine;
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t a = kRecId, c = 0;
+#pragma unroll
+        for (int w = 0; w < RB / 64; ++w) {
+            a = rec_then(a, s_rec[w], (uint32_t)w * 64 * RWW);
+            c += s_cnt[w];
+        }
+        tcnt[t] = c;
+        rec[t] = a;
+    }
+}
+
+// ---------------------------------------------------------------- LWW count pass
+template <bool BITS>
+__global__ __launch_bounds__(RB) void k_lww_read(crdt_tuples T, uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                                                 uint32_t *__restrict__ tcnt, uint64_t *__restrict__ bits) {
+    __shared__ uint32_t s_cnt[RB / 64];
+    uint64_t n;
+    if (!read_len(n_max, n_dev, &n)) return;
+    const uint64_t t = blockIdx.x, tb = t * RT;
+    if (tb >= n) return;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i0 = tb + (uint64_t)wv * (64 * RWW);
+    uint64_t k[RWW], kn[RWW], kp[RWW];
+    uint8_t tm[RWW];
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+        const uint64_t a = i < n ? i : n - 1, b = i + 1 < n ? i + 1 : n - 1;
+        k[j] = T.key[a];
+        kn[j] = T.key[b];
+        kp[j] = T.key[a > 0 ? a - 1 : 0];
+        tm[j] = T.tomb[a];
+    }
+    uint32_t cnt = 0;
+    uint64_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+        // the last tuple of a key's run carries the key's maximal tag
+        const bool ke = i < n && !(i + 1 < n && k[j] == kn[j]);
+        bool live = ke && tm[j] == 0;
+        if (ke && i > 0 && kp[j] == k[j]) {              // the key has more tuples: the tag's FIRST copy decides
+            const uint64_t x = T.ts[i];
+            const uint32_t y = T.rep[i];
+            uint64_t w = i;
+            while (w > 0 && T.key[w - 1] == k[j] && T.ts[w - 1] == x && T.rep[w - 1] == y) --w;
+            live = T.tomb[w] == 0;
+        }
+        const uint64_t e = __ballot(live);
+        cnt += (uint32_t)__popcll(e);
+        if (lane == j) mine = e;
+    }
+    if (BITS && lane < RWW) bits[t * RNW + (uint64_t)wv * RWW + lane] = mine;
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+#pragma unroll
+        for (int w = 0; w < RB / 64; ++w) c += s_cnt[w];
+        tcnt[t] = c;
+    }
+}
+
+// ---------------------------------------------------------------- carry + scan
+// One workgroup, rounds of up to kReadScanMax tiles (k_chunk_scan's scheme,
+// a contiguous run of 16 tiles per thread): with rec, the carries into every
+// tile as a scan of the records' functions, the first key end of each tile
+// re-decided under its carry (emit bit in bits, when given, and the count);
+// then the counts to offsets (ic, when given; ic[tiles] = the total) and the
+// total to *count.
+__global__ __launch_bounds__(1024) void k_read_scan(uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                                                    uint32_t *__restrict__ tcnt, const uint32_t *__restrict__ rec,
+                                                    uint64_t *__restrict__ bits, uint64_t *__restrict__ ic,
+                                                    uint64_t *__restrict__ count, uint32_t *__restrict__ err) {
+    constexpr int K = kReadScanMax / 1024;
+    __shared__ uint32_t s_f[16];
+    __shared__ uint64_t s_c[16];
+    uint64_t n;
+    if (!read_len(n_max, n_dev, &n)) {
+        if (threadIdx.x == 0) {
+            *count = ~0ull;
+            atomicOr(err, CRDT_DEV_RANGE);
+        }
+        return;
+    }
+    const uint64_t nt = (n + RT - 1) / RT;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t state = 0;                                  // the carry into the round's first tile
+    uint64_t base = 0;
+    for (uint64_t c0 = 0; c0 < nt; c0 += kReadScanMax) {
+        const uint64_t b = c0 + (uint64_t)threadIdx.x * K;
+        uint32_t v[K];
+#pragma unroll
+        for (int q = 0; q < K; ++q) v[q] = b + q < nt ? tcnt[b + q] : 0u;
+        if (rec) {
+            uint32_t rr[K], f = kRecId;
+#pragma unroll
+            for (int q = 0; q < K; ++q) {
+                rr[q] = b + q < nt ? rec[b + q] : kRecId;
+                f = fn_then(f, rr[q] & 0xffu);
+            }
+            uint32_t x = f;                              // inclusive scan over the wave's threads
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t y = __shfl_up(x, o, 64);
+                if (lane >= o) x = fn_then(y, x);
+            }
+            if (lane == 63) s_f[w] = x;
+            uint32_t ex = __shfl_up(x, 1, 64);
+            if (lane == 0) ex = kRecId;
+            __syncthreads();
+            uint32_t pre = kRecId, tot = kRecId;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                if (q < w) pre = fn_then(pre, s_f[q]);
+                tot = fn_then(tot, s_f[q]);
+            }
+            uint32_t s = rec_f(fn_then(pre, ex), state);
+#pragma unroll
+            for (int q = 0; q < K; ++q) {
+                if (b + q < nt && (rr[q] & kRecKE) && rec_e(rr[q], s) != rec_e(rr[q], 0)) {
+                    const uint32_t p = rec_pos(rr[q]);
+                    if (bits) bits[(b + q) * RNW + (p >> 6)] ^= 1ull << (p & 63);
+                    v[q] += rec_e(rr[q], s) ? 1u : 0xffffffffu;
+                }
+                s = rec_f(rr[q], s);
+            }
+            state = rec_f(tot, state);
+        }
+        uint64_t sum = 0;
+#pragma unroll
+        for (int q = 0; q < K; ++q) sum += v[q];
+        uint64_t x = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) s_c[w] = x;
+        __syncthreads();
+        uint64_t run = base + x - sum, tot = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            run += q < w ? s_c[q] : 0;
+            tot += s_c[q];
+        }
+        if (ic) {
+#pragma unroll
+            for (int q = 0; q < K; ++q) {
+                if (b + q < nt) ic[b + q] = run;
+                run += v[q];
+            }
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (ic) ic[nt] = base;
+        *count = base;
+    }
+}
+
+// ---------------------------------------------------------------- write pass
+__global__ __launch_bounds__(RB) void k_read_write(const uint64_t *__restrict__ key, uint64_t n_max,
+                                                   const uint64_t *__restrict__ n_dev,
+                                                   const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
+                                                   uint64_t *__restrict__ out, uint32_t *__restrict__ err) {
+    uint64_t n;
+    if (!read_len(n_max, n_dev, &n)) return;
+    const uint64_t t = blockIdx.x, tb = t * RT;
+    if (tb >= n) return;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t wd = lane < RNW ? bits[t * RNW + lane] : 0ull;   // every wave holds the tile's words
+    const uint32_t pc = (uint32_t)__popcll(wd);
+    uint32_t x = pc;
+#pragma unroll
+    for (int o = 1; o < RNW; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    const uint32_t ex = x - pc;
+    const uint64_t base = ic[t];
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const int q = wv * RWW + j;
+        const uint64_t wq = (uint64_t)__shfl((unsigned long long)wd, q, 64);
+        const uint32_t pq = __shfl(ex, q, 64);
+        if ((wq >> lane) & 1) {
+            const uint64_t i = tb + (uint64_t)q * 64 + lane;
+            const uint64_t at = base + pq + (uint32_t)__popcll(wq & ((1ull << lane) - 1));
+            if (i < n && at < n_max) out[at] = key[i];   // (a bitmap of this call's count pass never fails this)
+            else bad = true;
+        }
+    }
+    if (bad) atomicOr(err, CRDT_DEV_RANGE);
+}
+
+// ---------------------------------------------------------------- membership
+// out[i] = probes[i] occurs in v[0 .. n): one probe per lane, the binary
+// search of crdt_u64_lower_bound and an equality test.  (Its loads are what
+// it costs, one cache line each until the last few steps share one: a 4-ary
+// step per lane, 3 pivots in flight, measured 1.17x the time at 1M probes
+// into 7M keys, a 16-ary one 2.3x -- DESIGN.md §5.12.)
+__global__ void k_u64_contains(const uint64_t *__restrict__ v, uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                               const uint64_t *__restrict__ probes, uint64_t m, uint8_t *__restrict__ out,
+                               uint32_t *__restrict__ err) {
+    uint64_t n;
+    if (!read_len(n_max, n_dev, &n)) {
+        n = 0;
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, CRDT_DEV_RANGE);
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t x = probes[i];
+        uint64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const uint64_t mid = lo + ((hi - lo) >> 1);
+            if (v[mid] < x) lo = mid + 1;
+            else hi = mid;
+        }
+        out[i] = lo < n && v[lo] == x ? 1 : 0;
+    }
+}
+
+static bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return an && bn && x < y + bn && y < x + an;
+}
+
+}  // namespace crdt
+
+using namespace crdt;
+
+extern "C" int crdt_set_elements(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
+                                 uint64_t *keys_out, uint64_t *count) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!t || !count || (mode != CRDT_SET_LWW && mode != CRDT_SET_ORSET)) return CRDT_E_INVAL;
+    if (n_max >= (1ULL << 62)) return CRDT_E_RANGE;
+    if (n_max) {
+        if (!t->key || !t->ts || !t->rep || !t->tomb) return CRDT_E_INVAL;
+        if ((((uintptr_t)t->key | (uintptr_t)t->ts) & 7) | ((uintptr_t)t->rep & 3)) return CRDT_E_INVAL;
+        if (keys_out && (((uintptr_t)keys_out & 7) || ranges_overlap(keys_out, n_max * 8, t->key, n_max * 8) ||
+                         ranges_overlap(keys_out, n_max * 8, t->ts, n_max * 8) ||
+                         ranges_overlap(keys_out, n_max * 8, t->rep, n_max * 4) ||
+                         ranges_overlap(keys_out, n_max * 8, t->tomb, n_max)))
+            return CRDT_E_INVAL;
+    }
+    const size_t ntiles = (n_max + RT - 1) / RT;
+    if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;
+    const size_t need = Carve::round((ntiles + 1) * 4) + Carve::round((ntiles + 1) * 4) +
+                        Carve::round((ntiles + 1) * 8) + Carve::round((ntiles * RNW + 1) * 8) + 1024;
+    rc = ws_reserve(ctx, need);
+    if (rc) return rc;
+    Carve w(ctx->ws);
+    uint32_t *tcnt = w.take<uint32_t>(ntiles + 1);
+    uint32_t *rec = w.take<uint32_t>(ntiles + 1);
+    uint64_t *ic = w.take<uint64_t>(ntiles + 1);
+    uint64_t *bits = w.take<uint64_t>(ntiles * RNW + 1);
+    const bool lww = mode == CRDT_SET_LWW, wr = keys_out != nullptr;
+    const hipStream_t s = ctx->stream;
+    if (ntiles) {
+        const unsigned g = (unsigned)ntiles;
+        if (lww && wr) k_lww_read<true><<<g, RB, 0, s>>>(*t, n_max, n_dev, tcnt, bits);
+        else if (lww) k_lww_read<false><<<g, RB, 0, s>>>(*t, n_max, n_dev, tcnt, bits);
+        else if (wr) k_or_read<true><<<g, RB, 0, s>>>(*t, n_max, n_dev, tcnt, rec, bits);
+        else k_or_read<false><<<g, RB, 0, s>>>(*t, n_max, n_dev, tcnt, rec, bits);
+    }
+    k_read_scan<<<1, 1024, 0, s>>>(n_max, n_dev, tcnt, lww ? nullptr : rec, wr ? bits : nullptr, wr ? ic : nullptr,
+                                   count, ctx->dev_status);
+    if (ntiles && wr)
+        k_read_write<<<(unsigned)ntiles, RB, 0, s>>>(t->key, n_max, n_dev, bits, ic, keys_out, ctx->dev_status);
+    return check_launch(ctx);
+}
+
+extern "C" int crdt_u64_contains(crdt_ctx *ctx, const uint64_t *sorted, size_t n_max, const uint64_t *n_dev,
+                                 const uint64_t *probes, size_t m, uint8_t *out) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (n_max >= (1ULL << 62)) return CRDT_E_RANGE;
+    if (m == 0) return CRDT_OK;
+    if (!probes || !out || (n_max && !sorted) || ((uintptr_t)sorted & 7) || ((uintptr_t)probes & 7))
+        return CRDT_E_INVAL;
+    k_u64_contains<<<grid_for(m, 256, (unsigned)ctx->num_cus * 8), 256, 0, ctx->stream>>>(
+        sorted, n_max, n_dev, probes, m, out, ctx->dev_status);
+    return check_launch(ctx);
+}

@@ -301,6 +301,52 @@ class Engine:
                    probes.numel(), out.data_ptr())
         return out
 
+    # -- set reads: which keys are in a merged state (crdt_set_elements / crdt_u64_contains)
+    def set_elements(self, t: TupleSet, lww: bool, n_dev: torch.Tensor | None = None,
+                     out: torch.Tensor | None = None, count: torch.Tensor | None = None):
+        """Live keys of the sorted set state ``t`` (ascending, each once):
+        returns (keys, count), device tensors, no synchronisation -- keys is
+        int64 storage of capacity len(t), its first ``count`` entries valid.
+        ``n_dev`` (int64[1] on the device, e.g. a merge's count): only the
+        first n_dev tuples of t are read; a value over len(t) leaves count =
+        2^64 - 1 and raises CRDT_DEV_RANGE in :meth:`device_status`."""
+        n = len(t)
+        out = torch.empty(max(n, 1), dtype=torch.int64, device=self.device) if out is None else out
+        self._check(out, itemsize=8)
+        if out.numel() < n:
+            raise ValueError("set_elements: out holds fewer keys than t has tuples")
+        return out, self._set_read(t, lww, n_dev, out, count)
+
+    def set_cardinality(self, t: TupleSet, lww: bool, n_dev: torch.Tensor | None = None,
+                        count: torch.Tensor | None = None) -> torch.Tensor:
+        """Number of live keys of ``t`` (int64[1] on the device, no
+        synchronisation): one pass over the tuples, nothing else written."""
+        return self._set_read(t, lww, n_dev, None, count)
+
+    def _set_read(self, t: TupleSet, lww: bool, n_dev, out, count) -> torch.Tensor:
+        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        self._check(t.key, t.ts, count, itemsize=8)
+        self._check(t.rep, itemsize=4)
+        self._check(t.tomb, itemsize=1)
+        if n_dev is not None:
+            self._check(n_dev, itemsize=8)
+        ct = t.c()
+        self._call("crdt_set_elements", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev), _ptr(out),
+                   count.data_ptr())
+        return count
+
+    def keys_contain(self, sorted_keys: torch.Tensor, probes: torch.Tensor,
+                     n_dev: torch.Tensor | None = None) -> torch.Tensor:
+        """uint8[i] = 1 iff probes[i] is among the first n_dev (default: all)
+        of the ascending uint64 ``sorted_keys`` (crdt_u64_contains)."""
+        self._check(sorted_keys, probes, itemsize=8)
+        if n_dev is not None:
+            self._check(n_dev, itemsize=8)
+        res = torch.empty(probes.numel(), dtype=torch.uint8, device=self.device)
+        self._call("crdt_u64_contains", _ptr(sorted_keys), sorted_keys.numel(), _ptr(n_dev), _ptr(probes),
+                   probes.numel(), _ptr(res))
+        return res
+
     def tuples_merge(self, a: TupleSet, b: TupleSet, out: TupleSet | None = None) -> TupleSet:
         """Stable merge of two sorted tuple arrays, every tuple kept (a's
         copies first on an equal tag): crdt_tuples_merge."""

@@ -328,6 +328,27 @@ def sharded_refmerge(eng, packed: dict, group=None) -> dict:
     return eng.refmerge_finalize(packed, acc, out)
 
 
+def set_cardinality(comm: "Comm", outs, counts_dev, lww: bool = True):
+    """Number of live keys of a distributed set population: ``outs`` /
+    ``counts_dev`` as :meth:`Comm.set_merge_local_dev` returns them (member
+    i's own key range of the merged state, its length on the device).  The
+    ranges are key-disjoint, so the global cardinality is every member's own
+    (crdt_set_elements without a key output, chained off the device count on
+    the member's stream) summed by crdt_shard_allreduce.  Returns per-member
+    int64[1] device tensors, each the global count; :meth:`Comm.sync` before
+    reading them."""
+    if len(outs) != comm.members or len(counts_dev) != comm.members:
+        raise ValueError(f"expected one set and one count per member ({comm.members})")
+    cards = [torch.empty(1, dtype=torch.int64, device=d) for d in comm.devices]
+    for i, (o, c, card) in enumerate(zip(outs, counts_dev, cards)):
+        ctx = C.c_void_p()
+        comm._call("crdt_shard_member_ctx", i, C.byref(ctx))
+        ct = o.c()
+        _lib.call("crdt_set_elements", ctx, 0 if lww else 1, C.byref(ct), len(o), c.data_ptr(), None,
+                  card.data_ptr(), ctx=ctx)
+    return comm.allreduce(cards, "sum")
+
+
 # ---------------------------------------------------------------- native RCCL communicator
 class Comm:
     """The C-ABI's own RCCL communicator (crdt_shard_*, csrc/shard.hip).

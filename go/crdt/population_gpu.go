@@ -160,6 +160,30 @@ func (m *D2Merger) Enqueue(a, b, out *C.crdt_tuples, countDev *C.uint64_t) error
 	return status(C.crdt_lww_merge_unsorted_planned(gpuCtx, &m.plan, a, m.na, b, m.nb, out, countDev))
 }
 
+// SetElements: the live keys of a sorted set state already in HBM (what the
+// reference serves as CurrentState on GET /data, main.go:129-139), ascending
+// and each once into keysOutDev (capacity nMax keys), their number into
+// countDev.  nDev (nil: nMax tuples) chains the read off a merge's device
+// count with no read-back.  Enqueued: crdt_ctx_sync before reading.
+func SetElements(lww bool, t *C.crdt_tuples, nMax int, nDev, keysOutDev, countDev *C.uint64_t) error {
+	mode := C.int(C.CRDT_SET_ORSET)
+	if lww {
+		mode = C.int(C.CRDT_SET_LWW)
+	}
+	return status(C.crdt_set_elements(gpuCtx, mode, t, C.size_t(nMax), nDev, keysOutDev, countDev))
+}
+
+// SetCardinality: the number of live keys alone (one pass, no key output).
+func SetCardinality(lww bool, t *C.crdt_tuples, nMax int, nDev, countDev *C.uint64_t) error {
+	return SetElements(lww, t, nMax, nDev, nil, countDev)
+}
+
+// KeysContain: outDev[i] = 1 iff probesDev[i] is among the first *nDev (nil:
+// nMax) of the ascending keys SetElements wrote.
+func KeysContain(keysDev *C.uint64_t, nMax int, nDev, probesDev *C.uint64_t, m int, outDev *C.uint8_t) error {
+	return status(C.crdt_u64_contains(gpuCtx, keysDev, C.size_t(nMax), nDev, probesDev, C.size_t(m), outDev))
+}
+
 // RCCLInfo: which RCCL the process runs (for the service's logs / metrics).
 func RCCLInfo() (int, string) {
 	var v C.int

@@ -234,6 +234,37 @@ int crdt_tuples_sort(crdt_ctx *ctx, const crdt_tuples *in, size_t n, crdt_tuples
  * probes (device arrays): key-range sharding of a sorted set (§8(e) D). */
 int crdt_u64_lower_bound(crdt_ctx *ctx, const uint64_t *sorted_dev, size_t n, const uint64_t *probes_dev,
                          size_t m, uint64_t *out_dev);
+/* ---- set reads: which keys are in a merged set state (the reference serves
+ * its materialised CurrentState on GET /data, main.go:129-139).
+ * Live keys of a set state t sorted by (key, ts, rep), ascending, each once,
+ * into keys_out_dev; their number into *count_dev (device uint64).  mode as
+ * in crdt_set_merge_plan.  OR-Set: a tag is live iff none of its copies is
+ * tombstoned, a key is a member iff it has a live tag.  LWW: a key is a
+ * member iff the first copy of its maximal (ts, rep) tag has tomb == 0 (the
+ * winner crdt_lww_merge keeps).  Either way the keys of merge(t, {}) whose
+ * (OR-Set: any) output tuple has tomb == 0.  keys_out_dev may be NULL:
+ * cardinality only (one pass, nothing written but the count).
+ * n_dev (device uint64, may be NULL) gives the tuple count on the device, as
+ * crdt_seg_gather2_n does: NULL -> n_max tuples; *n_dev <= n_max -> the first
+ * *n_dev (pass a merge's out_count_dev and its output capacity: no read-back
+ * between the merge and the read); *n_dev > n_max (the ~0 a planned merge
+ * leaves on a plan miss included) -> no tuple is touched, *count_dev = ~0 and
+ * CRDT_DEV_RANGE is raised.  No kernel reads at or past min(*n_dev, n_max).
+ * Stream-ordered, no host synchronisation (capturable after
+ * crdt_ctx_reserve).  keys_out_dev holds >= n_max keys and must not overlap
+ * t; key / ts / rep naturally aligned (the merges' rule).  CRDT_E_INVAL: NULL
+ * ctx / t / count_dev, bad mode, misalignment, overlap; CRDT_E_RANGE: n_max
+ * >= 2^62.  n_max == 0 launches nothing but the count store. */
+#define CRDT_SET_LWW   0
+#define CRDT_SET_ORSET 1
+int crdt_set_elements(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
+                      uint64_t *keys_out_dev, uint64_t *count_dev);
+/* out[i] = 1 iff probes[i] occurs in sorted_dev[0 .. n) (unsigned order), for
+ * m probes; n from n_max / n_dev as above (*n_dev > n_max: out all zero and
+ * CRDT_DEV_RANGE).  Membership in the keys crdt_set_elements wrote, with its
+ * count_dev as n_dev.  Stream-ordered, no host synchronisation. */
+int crdt_u64_contains(crdt_ctx *ctx, const uint64_t *sorted_dev, size_t n_max, const uint64_t *n_dev,
+                      const uint64_t *probes_dev, size_t m, uint8_t *out_dev);
 /* Sortedness check (host-facing validation): *bad_dev = number of adjacent
  * pairs with t[i] > t[i+1]. */
 int crdt_tuples_count_unsorted(crdt_ctx *ctx, const crdt_tuples *t, size_t n,
