@@ -11,7 +11,7 @@
 KNOB(g_join_unroll, 1, "join.unroll", v == 1 || v == 2 || v == 4 || v == 8)
 KNOB(g_join_nontemporal, 1, "join.nontemporal", v == 0 || v == 1)
 KNOB(g_join_blocks_per_cu, 2, "join.blocks_per_cu", v >= 1 && v <= 64)
-KNOB(g_fold_unroll, 8, "fold.unroll", v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32)
+KNOB(g_fold_unroll, 8, "fold.unroll", v == 1 || v == 2 || v == 4 || v == 8 || v == 16)
 KNOB(g_fold_nontemporal, 1, "fold.nontemporal", v == 0 || v == 1)
 KNOB(g_fold_blocks_per_cu, 1, "fold.blocks_per_cu", v >= 1 && v <= 64)
 KNOB(g_vclock_pairs_per_wave, 32, "vclock.pairs_per_wave", v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32)
