@@ -347,6 +347,50 @@ class Engine:
                    probes.numel(), _ptr(res))
         return res
 
+    # -- set deltas: the tuples of src that dst lacks (crdt_set_delta)
+    def set_delta(self, src: TupleSet, dst: TupleSet, lww: bool, n_src_dev: torch.Tensor | None = None,
+                  n_dst_dev: torch.Tensor | None = None, out: TupleSet | None = None,
+                  count: torch.Tensor | None = None, trim: bool = False):
+        """The smallest D with merge(dst, D) == merge(dst, src), dst the left
+        (tie-winning) operand, in ascending tuple order: returns (D, count),
+        device-resident, no synchronisation -- D of capacity len(src), its
+        first ``count`` tuples valid.  ``n_src_dev`` / ``n_dst_dev`` (int64[1]
+        on the device, e.g. a merge's count): only so many leading tuples of
+        that side are read; a value over the side's length leaves count =
+        2^64 - 1 and raises CRDT_DEV_RANGE in :meth:`device_status`.  With
+        ``trim`` the device status is checked and the sliced D returned."""
+        out = TupleSet.empty(max(len(src), 1), self.device) if out is None else out
+        if len(out) < len(src):
+            raise ValueError("set_delta: out holds fewer tuples than src")
+        count = self._set_delta(src, dst, lww, n_src_dev, n_dst_dev, out, count)
+        if trim:
+            self.check_device()
+            return out.slice(int(count.item()))
+        return out, count
+
+    def set_delta_count(self, src: TupleSet, dst: TupleSet, lww: bool, n_src_dev: torch.Tensor | None = None,
+                        n_dst_dev: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(delta(src, dst)) alone (int64[1] on the device, no
+        synchronisation); 0 iff dst already holds all of src -- the in-sync
+        test.  Nothing is written but the count."""
+        return self._set_delta(src, dst, lww, n_src_dev, n_dst_dev, None, count)
+
+    def _set_delta(self, src: TupleSet, dst: TupleSet, lww: bool, n_src_dev, n_dst_dev, out, count) -> torch.Tensor:
+        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        self._check(count, itemsize=8)
+        for s in (src, dst) + (() if out is None else (out,)):
+            self._check(s.key, s.ts, itemsize=8)
+            self._check(s.rep, itemsize=4)
+            self._check(s.tomb, itemsize=1)
+        for n_dev in (n_src_dev, n_dst_dev):
+            if n_dev is not None:
+                self._check(n_dev, itemsize=8)
+        cs, cd = src.c(), dst.c()
+        co = None if out is None else out.c()
+        self._call("crdt_set_delta", 0 if lww else 1, C.byref(cs), len(src), _ptr(n_src_dev), C.byref(cd), len(dst),
+                   _ptr(n_dst_dev), None if co is None else C.byref(co), count.data_ptr())
+        return count
+
     def tuples_merge(self, a: TupleSet, b: TupleSet, out: TupleSet | None = None) -> TupleSet:
         """Stable merge of two sorted tuple arrays, every tuple kept (a's
         copies first on an equal tag): crdt_tuples_merge."""

@@ -184,6 +184,33 @@ func KeysContain(keysDev *C.uint64_t, nMax int, nDev, probesDev *C.uint64_t, m i
 	return status(C.crdt_u64_contains(gpuCtx, keysDev, C.size_t(nMax), nDev, probesDev, C.size_t(m), outDev))
 }
 
+// SetDelta: the tuples of the sorted set state src that dst lacks -- the
+// smallest D with merge(dst, D) == merge(dst, src), dst the tie-winning side --
+// in ascending order into out (capacity nsMax tuples), their number into
+// countDev.  What a gossip pull needs to ship instead of the entire Diff
+// (main.go:153-170, :245-256).  nsDev / ndDev (nil: all nMax tuples of the
+// side) chain the call off device counts with no read-back.  An empty src
+// (nsMax == 0) stores a count of 0 and touches neither side.  Enqueued:
+// crdt_ctx_sync before reading.
+func SetDelta(lww bool, src *C.crdt_tuples, nsMax int, nsDev *C.uint64_t, dst *C.crdt_tuples, ndMax int,
+	ndDev *C.uint64_t, out *C.crdt_tuples, countDev *C.uint64_t) error {
+	if src == nil || dst == nil || countDev == nil || nsMax < 0 || ndMax < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	mode := C.int(C.CRDT_SET_ORSET)
+	if lww {
+		mode = C.int(C.CRDT_SET_LWW)
+	}
+	return status(C.crdt_set_delta(gpuCtx, mode, src, C.size_t(nsMax), nsDev, dst, C.size_t(ndMax), ndDev, out, countDev))
+}
+
+// SetDeltaCount: the size of that delta alone (nothing stored but the count);
+// 0 iff dst already holds all of src -- the in-sync test of an anti-entropy loop.
+func SetDeltaCount(lww bool, src *C.crdt_tuples, nsMax int, nsDev *C.uint64_t, dst *C.crdt_tuples, ndMax int,
+	ndDev, countDev *C.uint64_t) error {
+	return SetDelta(lww, src, nsMax, nsDev, dst, ndMax, ndDev, nil, countDev)
+}
+
 // RCCLInfo: which RCCL the process runs (for the service's logs / metrics).
 func RCCLInfo() (int, string) {
 	var v C.int

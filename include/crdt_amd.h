@@ -265,6 +265,35 @@ int crdt_set_elements(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_ma
  * count_dev as n_dev.  Stream-ordered, no host synchronisation. */
 int crdt_u64_contains(crdt_ctx *ctx, const uint64_t *sorted_dev, size_t n_max, const uint64_t *n_dev,
                       const uint64_t *probes_dev, size_t m, uint8_t *out_dev);
+/* ---- set deltas: the tuples of one set state that another lacks (the
+ * reference's gossip pull ships the entire Diff every round, main.go:153-170
+ * and :245-256).  delta(src, dst) = the smallest set of tuples D with
+ * merge(dst, D) == merge(dst, src) bit for bit, dst the left (tie-winning)
+ * operand of crdt_lww_merge / crdt_orset_merge; both sides sorted by (key, ts,
+ * rep), copies of one tag in any order on either side.  OR-Set: a tag of src
+ * ships iff dst holds no copy of it, or the OR of src's copies' tombs is 1 and
+ * that of dst's is 0; once, with src's tomb-OR.  LWW: src's winner of a key
+ * (its maximal (ts, rep) tag, the tomb of that tag's first copy) ships iff dst
+ * holds no tuple of the key or src's maximal tag is strictly greater than
+ * dst's (an equal tag stays: the merge keeps dst's copy).  D is written to
+ * out in ascending tuple order, its size to *count_dev (device uint64);
+ * delta(src, {}) == merge(src, {}), delta({}, dst) and delta(src, merge(dst,
+ * src)) are empty -- the in-sync test.  out may be NULL: the count alone (no
+ * bitmaps, no offsets, nothing stored but *count_dev).
+ * ns_dev / nd_dev follow crdt_set_elements' n_dev, each on its own: NULL ->
+ * all n_max tuples of the side; <= n_max -> the first so many; > n_max on
+ * either side -> no tuple of either side is touched, nothing is written to
+ * out, *count_dev = ~0 and CRDT_DEV_RANGE is raised.  No kernel reads an index
+ * at or past min(*n_dev, n_max) of its side.  Stream-ordered, no host
+ * synchronisation (capturable after crdt_ctx_reserve).  out holds >= ns_max
+ * tuples and must not overlap src or dst.  CRDT_E_INVAL: NULL ctx / src / dst
+ * / count_dev, bad mode, NULL fields of a side with n_max > 0, key / ts / rep
+ * of any operand not naturally aligned, out overlapping an input;
+ * CRDT_E_RANGE: ns_max or nd_max >= 2^62 or more tiles than a launch holds.
+ * ns_max == 0 launches nothing but the count store. */
+int crdt_set_delta(crdt_ctx *ctx, int mode, const crdt_tuples *src, size_t ns_max, const uint64_t *ns_dev,
+                   const crdt_tuples *dst, size_t nd_max, const uint64_t *nd_dev, const crdt_tuples *out,
+                   uint64_t *count_dev);
 /* Sortedness check (host-facing validation): *bad_dev = number of adjacent
  * pairs with t[i] > t[i+1]. */
 int crdt_tuples_count_unsorted(crdt_ctx *ctx, const crdt_tuples *t, size_t n,
