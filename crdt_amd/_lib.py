@@ -180,6 +180,11 @@ SIGNATURES = {
                             C.POINTER(crdt_tuples), _P]),
     "crdt_orset_merge": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, C.POINTER(crdt_tuples), _SZ,
                               C.POINTER(crdt_tuples), _P]),
+    "crdt_lww_merge_src": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, C.POINTER(crdt_tuples), _SZ,
+                                C.POINTER(crdt_tuples), _P, _P]),
+    "crdt_orset_merge_src": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, C.POINTER(crdt_tuples), _SZ,
+                                  C.POINTER(crdt_tuples), _P, _P]),
+    "crdt_src_gather": (_I, [_CTX, _P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crdt_lww_merge_unsorted": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, C.POINTER(crdt_tuples), _SZ,
                                      C.POINTER(crdt_tuples), _P]),
     "crdt_orset_merge_unsorted": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, C.POINTER(crdt_tuples), _SZ,

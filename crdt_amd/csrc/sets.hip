@@ -321,153 +321,21 @@ __global__ __launch_bounds__(WT) void k_lww_write(crdt_tuples A, crdt_tuples B, 
                                                   const uint64_t *__restrict__ split,
                                                   const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
                                                   crdt_tuples out, uint64_t t0, uint32_t *__restrict__ err) {
-    constexpr int NWV = WT / 64, FI = (WH / 64) / NWV, CAP = WH + 3, P = LT / WH, WPP = LNW / P;
-    static_assert(LNW == 64 && WH * P == LT && FI * NWV * 64 == WH && WH == 4 * WT, "shape");
-    // (each field holds A's run then B's, each from its 16-byte aligned-down
-    // start by LDS-DMA: up to 64 bytes more than the elements)
-    __shared__ alignas(16) uint64_t s_key[CAP + 8];
-    __shared__ alignas(16) uint64_t s_ts[CAP + 8];
-    __shared__ alignas(16) uint32_t s_rep[CAP + 16];
-    __shared__ alignas(16) uint8_t s_tomb[CAP + 64];
-    const uint64_t t = t0 + blockIdx.x / P;
-    const uint32_t h = blockIdx.x % P;
-    const LwwTile b = lww_tile(split, t, na + nb);
-    const int lane = threadIdx.x & 63;
-    const uint64_t word_a = bits[t * 2 * LNW + lane], word_e = bits[t * 2 * LNW + LNW + lane];
-    const uint64_t ob = ic[t];                           // (with the split and bitmaps: no load after the barrier)
-    uint32_t pre_a = (uint32_t)__popcll(word_a), pre_e = (uint32_t)__popcll(word_e);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t ya = __shfl_up(pre_a, o), ye = __shfl_up(pre_e, o);
-        if (lane >= o) {
-            pre_a += ya;
-            pre_e += ye;
-        }
-    }
-    pre_a -= (uint32_t)__popcll(word_a);
-    pre_e -= (uint32_t)__popcll(word_e);
-    // every index below derives from the bitmaps: a tile whose bitmaps do not
-    // describe its counts raises CRDT_DEV_RANGE instead of reading out of range
-    if (!bitmaps_consistent(word_a, word_e, pre_a, LNW, b.na, b.n, lane)) {
-        if (threadIdx.x == 0 && blockIdx.x % P == 0) atomicOr(err, CRDT_DEV_RANGE);
-        return;
-    }
-    // the half's runs: A [ra, ra + ca), B [rb, rb + cb); staged from ra - 2 / rb - 1
-    const uint32_t ha = (uint32_t)__builtin_amdgcn_readlane(pre_a, WPP * h);       // A items before the part
-    const uint32_t ha1 = h + 1 == P ? b.na : (uint32_t)__builtin_amdgcn_readlane(pre_a, WPP * (h + 1));  // ... before its end
-    const uint32_t d0 = WH * h;
-    const uint32_t hn = b.n > d0 ? (b.n - d0 < (uint32_t)WH ? b.n - d0 : (uint32_t)WH) : 0;   // items in the part
-    if (hn == 0) return;
-    const size_t ra = b.i0 + ha, rb = b.j0 + (d0 - ha);
-    const uint32_t ca = ha1 - ha, cb = hn - ca;
-    const uint32_t na2 = ca + 2;                         // staged A: ra-2 .. ra+ca-1 (slots 0 .. ca+1)
-    // slot x of field f sits at LDS element x + (x < na2 ? oa[f] : ob[f])
-    int oa_k, ob_k, oa_t, ob_t, oa_r, ob_r, oa_m, ob_m;
-    {
-        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        const size_t ga = ra >= 2 ? ra - 2 : 0, gb = rb >= 1 ? rb - 1 : 0;   // first staged element of each side
-        const uint32_t ka = (uint32_t)(ra + ca - ga), kb = (uint32_t)(rb + cb - gb);
-        const int sa = (int)(ga - (ra - 2)), sb = (int)(gb - (rb - 1)) + (int)na2;   // their slots
-        uint32_t at = 0;
-        oa_k = dma_run<uint64_t, NWV>(A.key, ga, ka, s_key, &at, wv, lane) - sa;
-        ob_k = dma_run<uint64_t, NWV>(B.key, gb, kb, s_key, &at, wv, lane) - sb;
-        at = 0;
-        // (ts / rep / tomb read once, nontemporal: they do not evict the keys
-        // the count pass left in the Infinity Cache)
-        oa_t = dma_run<uint64_t, NWV, 2>(A.ts, ga, ka, s_ts, &at, wv, lane) - sa;
-        ob_t = dma_run<uint64_t, NWV, 2>(B.ts, gb, kb, s_ts, &at, wv, lane) - sb;
-        at = 0;
-        oa_r = dma_run<uint32_t, NWV, 2>(A.rep, ga, ka, s_rep, &at, wv, lane) - sa;
-        ob_r = dma_run<uint32_t, NWV, 2>(B.rep, gb, kb, s_rep, &at, wv, lane) - sb;
-        at = 0;
-        oa_m = dma_run<uint8_t, NWV, 2>(A.tomb, ga, ka, s_tomb, &at, wv, lane) - sa;
-        ob_m = dma_run<uint8_t, NWV, 2>(B.tomb, gb, kb, s_tomb, &at, wv, lane) - sb;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA has landed in LDS
-    }
-    __syncthreads();
-    const int wvu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    auto below = [&](uint64_t msk) -> uint32_t {        // set bits of msk below this lane
-        return __builtin_amdgcn_mbcnt_hi((uint32_t)(msk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)msk, 0u));
-    };
-    // staged fields of slot sl
-    auto tag_at = [&](uint32_t sl, uint64_t &k, uint64_t &ts, uint32_t &r) {
-        const bool sa = sl < na2;
-        k = s_key[(int)sl + (sa ? oa_k : ob_k)];
-        ts = s_ts[(int)sl + (sa ? oa_t : ob_t)];
-        r = s_rep[(int)sl + (sa ? oa_r : ob_r)];
-    };
-    auto tomb_at = [&](uint32_t sl) -> uint8_t { return s_tomb[(int)sl + (sl < na2 ? oa_m : ob_m)]; };
-#pragma unroll
-    for (int f = 0; f < FI; ++f) {
-        const int w = WPP * (int)h + wvu + NWV * f;      // the tile's word
-        const uint64_t wa = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(word_a >> 32), w) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((uint32_t)word_a, w);
-        const uint64_t we = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(word_e >> 32), w) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((uint32_t)word_e, w);
-        if (!((we >> lane) & 1)) continue;
-        const uint32_t pa = (uint32_t)__builtin_amdgcn_readlane(pre_a, w) + below(wa);   // A items before (tile)
-        const uint32_t rk = (uint32_t)__builtin_amdgcn_readlane(pre_e, w) + below(we);   // output rank
-        const uint32_t k = 64u * (uint32_t)w + (uint32_t)lane;                          // tile merge item
-        const uint32_t la = pa - ha, lb = (k - d0) - la; // A / B items of the half before this one
-        const bool is_a = (wa >> lane) & 1;
-        const size_t ai = ra + la;                       // A elements merged before this item
-        uint64_t key, ts;
-        uint32_t rep, xs;                                // the winner's staging slot
-        bool on_a;
-        size_t wi;
-        if (is_a) {                                      // an A run end whose key B does not hold
-            xs = la + 2;
-            tag_at(xs, key, ts, rep);
-            on_a = true;
-            wi = ai;
-        } else {                                         // B's run end; A's run end of the key just before it
-            const uint32_t bs = na2 + 1 + lb;
-            uint64_t kb_, tb, ka_ = 0, ta = 0;
-            uint32_t rb_, ra_ = 0;
-            tag_at(bs, kb_, tb, rb_);
-            const bool a_has = ai > 0 && (tag_at(la + 1, ka_, ta, ra_), ka_ == kb_);
-            const bool ya = a_has && (ta > tb || (ta == tb && ra_ >= rb_));   // A wins an equal tag
-            key = kb_;
-            on_a = ya;
-            xs = ya ? la + 1 : bs;
-            ts = ya ? ta : tb;
-            rep = ya ? ra_ : rb_;
-            wi = ya ? ai - 1 : rb + lb;
-        }
-        // the first copy of the winner's tag on its side: its staged
-        // predecessor, then (rare) global memory before the staging
-        uint8_t tomb = tomb_at(xs);
-        const uint32_t lo = on_a ? 0u : na2;             // first staged slot of the side
-        bool more = wi > 0;
-        uint32_t sl = xs;
-        while (more && sl > lo) {
-            uint64_t pk, pt;
-            uint32_t pr;
-            tag_at(sl - 1, pk, pt, pr);
-            if (pk != key || pt != ts || pr != rep) {
-                more = false;
-                break;
-            }
-            --sl;
-            --wi;
-            tomb = tomb_at(sl);
-            more = wi > 0;
-        }
-        if (more && sl == lo) {                          // the run of copies reaches past the staging
-            const size_t fc = first_copy(on_a ? A.key : B.key, on_a ? A.ts : B.ts, on_a ? A.rep : B.rep, wi, key, ts,
-                                         rep);
-            tomb = (on_a ? A.tomb : B.tomb)[fc];
-        }
-        const uint64_t o = ob + rk;
-        if (o >= na + nb) {                              // (consistent bitmaps never get here)
-            atomicOr(err, CRDT_DEV_RANGE);
-            continue;
-        }
-        out.key[o] = key;
-        out.ts[o] = ts;
-        out.rep[o] = rep;
-        out.tomb[o] = tomb;
-    }
+    constexpr bool SRC = false;                          // (sets_lww_write.inc: no source indices)
+    constexpr int64_t *src = nullptr;
+#include "sets_lww_write.inc"
+}
+
+// k_lww_write that also stores every output's source index (crdt_lww_merge_src)
+template <int WH = LWH, int WT = LWT>
+__global__ __launch_bounds__(WT) void k_lww_write_src(crdt_tuples A, crdt_tuples B, size_t na, size_t nb,
+                                                      const uint64_t *__restrict__ split,
+                                                      const uint64_t *__restrict__ bits,
+                                                      const uint64_t *__restrict__ ic, crdt_tuples out,
+                                                      int64_t *__restrict__ src, uint64_t t0,
+                                                      uint32_t *__restrict__ err) {
+    constexpr bool SRC = true;
+#include "sets_lww_write.inc"
 }
 
 // ---------------------------------------------------------------- OR-Set, two passes
@@ -744,116 +612,21 @@ __global__ __launch_bounds__(WT) void k_or_write(crdt_tuples A, crdt_tuples B, s
                                                  const uint64_t *__restrict__ split,
                                                  const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
                                                  crdt_tuples out, uint64_t t0, uint32_t *__restrict__ err) {
-    constexpr int NWV = WT / 64, P = OT / WH, WPP = ONW / P, FI = WPP / NWV, CAP = WH + 2;
-    static_assert(FI * NWV == WPP && WH * P == OT && ONW <= 64 && WH == 4 * WT, "shape");
-    __shared__ alignas(16) uint64_t s_key[CAP + 8];
-    __shared__ alignas(16) uint64_t s_ts[CAP + 8];
-    __shared__ alignas(16) uint32_t s_rep[CAP + 16];
-    __shared__ alignas(16) uint8_t s_tomb[CAP + 64];
-    const uint64_t t = t0 + blockIdx.x / P;
-    const uint32_t h = blockIdx.x % P;
-    const LwwTile b = or_tile(split, t, na + nb);
-    const int lane = threadIdx.x & 63;
-    const bool wl_ok = lane < ONW;
-    // split, bitmap words and offset loads issued together (none after the barrier)
-    const uint64_t word_a = wl_ok ? bits[t * 2 * ONW + lane] : 0, word_e = wl_ok ? bits[t * 2 * ONW + ONW + lane] : 0;
-    const uint64_t ob = ic[t];
-    uint32_t pre_a = (uint32_t)__popcll(word_a), pre_e = (uint32_t)__popcll(word_e);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t ya = __shfl_up(pre_a, o), ye = __shfl_up(pre_e, o);
-        if (lane >= o) {
-            pre_a += ya;
-            pre_e += ye;
-        }
-    }
-    pre_a -= (uint32_t)__popcll(word_a);
-    pre_e -= (uint32_t)__popcll(word_e);
-    if (!bitmaps_consistent(word_a, word_e, pre_a, ONW, b.na, b.n, lane)) {   // (see k_lww_write)
-        if (threadIdx.x == 0 && blockIdx.x % P == 0) atomicOr(err, CRDT_DEV_RANGE);
-        return;
-    }
-    // the part's runs: A [pa0, pa0 + ca), B [pb0, pb0 + cb) (tile-relative)
-    const uint32_t d0 = WH * h;
-    const uint32_t hn = b.n > d0 ? (b.n - d0 < (uint32_t)WH ? b.n - d0 : (uint32_t)WH) : 0;   // items in the part
-    if (hn == 0) return;
-    const uint32_t pa0 = P == 1 ? 0u : (uint32_t)__builtin_amdgcn_readlane(pre_a, WPP * h);
-    const uint32_t pa1 = h + 1 == P ? b.na : (uint32_t)__builtin_amdgcn_readlane(pre_a, WPP * (h + 1));
-    const uint32_t ca = pa1 - pa0, cb = hn - ca, pb0 = d0 - pa0;
-    const size_t ga = b.i0 + pa0, gb = b.j0 + pb0;       // global index of each run's first element
-    // staged by LDS-DMA: A run (slots 0 .. ca-1), then B run (slots ca ..),
-    // every field once; slot x of field f at LDS element x + (x < ca ? oa[f] : ob[f])
-    int oa_k, ob_k, oa_t, ob_t, oa_r, ob_r, oa_m, ob_m;
-    {
-        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        const int sb = (int)ca;
-        uint32_t at = 0;
-        oa_k = dma_run<uint64_t, NWV>(A.key, ga, ca, s_key, &at, wv, lane);
-        ob_k = dma_run<uint64_t, NWV>(B.key, gb, cb, s_key, &at, wv, lane) - sb;
-        at = 0;
-        oa_t = dma_run<uint64_t, NWV>(A.ts, ga, ca, s_ts, &at, wv, lane);
-        ob_t = dma_run<uint64_t, NWV>(B.ts, gb, cb, s_ts, &at, wv, lane) - sb;
-        at = 0;
-        oa_r = dma_run<uint32_t, NWV>(A.rep, ga, ca, s_rep, &at, wv, lane);
-        ob_r = dma_run<uint32_t, NWV>(B.rep, gb, cb, s_rep, &at, wv, lane) - sb;
-        at = 0;
-        oa_m = dma_run<uint8_t, NWV>(A.tomb, ga, ca, s_tomb, &at, wv, lane);
-        ob_m = dma_run<uint8_t, NWV>(B.tomb, gb, cb, s_tomb, &at, wv, lane) - sb;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA has landed in LDS
-    }
-    __syncthreads();
-    const int wvu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    auto below = [&](uint64_t msk) -> uint32_t {        // set bits of msk below this lane
-        return __builtin_amdgcn_mbcnt_hi((uint32_t)(msk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)msk, 0u));
-    };
-#pragma unroll
-    for (int f = 0; f < FI; ++f) {
-        const int w = WPP * (int)h + wvu + NWV * f;      // the tile's word
-        // (readlane returns int: widen through uint32_t, never sign-extend)
-        const uint64_t wa = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(word_a >> 32), w) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((uint32_t)word_a, w);
-        const uint64_t we = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(word_e >> 32), w) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((uint32_t)word_e, w);
-        if (!((we >> lane) & 1)) continue;
-        const uint32_t la = (uint32_t)__builtin_amdgcn_readlane(pre_a, w) + below(wa) - pa0;   // A items before (part)
-        const uint32_t rk = (uint32_t)__builtin_amdgcn_readlane(pre_e, w) + below(we);         // output rank (tile)
-        const uint32_t k = 64u * (uint32_t)w + (uint32_t)lane - d0;
-        const uint32_t lb = k - la;                      // B items before (part)
-        const bool is_a = (wa >> lane) & 1;
-        const uint32_t xs = is_a ? la : ca + lb;         // the first copy's slot
-        const int xo = is_a ? 0 : 1;
-        const uint64_t key = s_key[(int)xs + (xo ? ob_k : oa_k)], ts = s_ts[(int)xs + (xo ? ob_t : oa_t)];
-        const uint32_t rep = s_rep[(int)xs + (xo ? ob_r : oa_r)];
-        uint32_t tomb = 0;
-        // A's copies (an A first copy only), then B's from position lb:
-        // in the staging, then past the part in global memory (rare)
-        if (is_a) {
-            uint32_t s = la;
-            while (s < ca && s_key[(int)s + oa_k] == key && s_ts[(int)s + oa_t] == ts && s_rep[(int)s + oa_r] == rep)
-                tomb |= s_tomb[(int)(s++) + oa_m];
-            if (s == ca)
-                for (size_t g = ga + ca; g < na && A.key[g] == key && A.ts[g] == ts && A.rep[g] == rep; ++g)
-                    tomb |= A.tomb[g];
-        }
-        {
-            uint32_t s = lb;
-            while (s < cb && s_key[(int)(ca + s) + ob_k] == key && s_ts[(int)(ca + s) + ob_t] == ts &&
-                   s_rep[(int)(ca + s) + ob_r] == rep)
-                tomb |= s_tomb[(int)(ca + s++) + ob_m];
-            if (s == cb)
-                for (size_t g = gb + cb; g < nb && B.key[g] == key && B.ts[g] == ts && B.rep[g] == rep; ++g)
-                    tomb |= B.tomb[g];
-        }
-        const uint64_t o = ob + rk;
-        if (o >= na + nb) {                              // (consistent bitmaps never get here)
-            atomicOr(err, CRDT_DEV_RANGE);
-            continue;
-        }
-        out.key[o] = key;
-        out.ts[o] = ts;
-        out.rep[o] = rep;
-        out.tomb[o] = (uint8_t)tomb;
-    }
+    constexpr bool SRC = false;                          // (sets_or_write.inc: no source indices)
+    constexpr int64_t *src = nullptr;
+#include "sets_or_write.inc"
+}
+
+// k_or_write that also stores every output's source index (crdt_orset_merge_src)
+template <int WH = OT, int WT = OWT>
+__global__ __launch_bounds__(WT) void k_or_write_src(crdt_tuples A, crdt_tuples B, size_t na, size_t nb,
+                                                     const uint64_t *__restrict__ split,
+                                                     const uint64_t *__restrict__ bits,
+                                                     const uint64_t *__restrict__ ic, crdt_tuples out,
+                                                     int64_t *__restrict__ src, uint64_t t0,
+                                                     uint32_t *__restrict__ err) {
+    constexpr bool SRC = true;
+#include "sets_or_write.inc"
 }
 
 // The chunked two-pass schedule.  count(t0, n, s) / scan(t0, n, count_out,
@@ -886,8 +659,9 @@ static int two_pass(crdt_ctx *ctx, size_t ntiles, uint64_t *out_count, CountF co
     return check_launch(ctx);
 }
 
+// (src != nullptr: the _src write kernels, every output's source index beside it)
 static int lww_merge_keyruns(crdt_ctx *ctx, const crdt_tuples &A, size_t na, const crdt_tuples &B, size_t nb,
-                             const crdt_tuples &O, uint64_t *out_count) {
+                             const crdt_tuples &O, int64_t *src, uint64_t *out_count) {
     const size_t n = na + nb;
     const size_t ntiles = (n + LT - 1) / LT;
     if (ntiles >= 0x7fffffffULL || n >= (1ULL << 62)) return CRDT_E_RANGE;
@@ -913,6 +687,13 @@ static int lww_merge_keyruns(crdt_ctx *ctx, const crdt_tuples &A, size_t na, con
     };
     auto wr = [&](size_t t0, uint32_t nt, hipStream_t s) {
         const unsigned g = P * nt;
+        if (src) {
+            if (P == 2) k_lww_write_src<2048, 512><<<g, 512, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
+            else if (P == 8) k_lww_write_src<512, 128><<<g, 128, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
+            else if (P == 16) k_lww_write_src<256, 64><<<g, 64, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
+            else k_lww_write_src<1024, 256><<<g, 256, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
+            return;
+        }
         if (P == 2) k_lww_write<2048, 512><<<g, 512, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
         else if (P == 8) k_lww_write<512, 128><<<g, 128, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
         else if (P == 16) k_lww_write<256, 64><<<g, 64, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
@@ -923,7 +704,7 @@ static int lww_merge_keyruns(crdt_ctx *ctx, const crdt_tuples &A, size_t na, con
 }
 
 static int orset_merge_twopass(crdt_ctx *ctx, const crdt_tuples &A, size_t na, const crdt_tuples &B, size_t nb,
-                               const crdt_tuples &O, uint64_t *out_count) {
+                               const crdt_tuples &O, int64_t *src, uint64_t *out_count) {
     const size_t n = na + nb;
     const size_t ntiles = (n + OT - 1) / OT;
     if (ntiles >= 0x7fffffffULL || n >= (1ULL << 62)) return CRDT_E_RANGE;
@@ -949,6 +730,12 @@ static int orset_merge_twopass(crdt_ctx *ctx, const crdt_tuples &A, size_t na, c
     };
     auto wr = [&](size_t t0, uint32_t nt, hipStream_t s) {
         const unsigned g = P * nt;
+        if (src) {
+            if (P == 2) k_or_write_src<1024, 256><<<g, 256, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
+            else if (P == 4) k_or_write_src<512, 128><<<g, 128, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
+            else k_or_write_src<2048, 512><<<g, 512, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
+            return;
+        }
         if (P == 2) k_or_write<1024, 256><<<g, 256, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
         else if (P == 4) k_or_write<512, 128><<<g, 128, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
         else k_or_write<2048, 512><<<g, 512, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
@@ -1156,14 +943,33 @@ static bool dma_aligned(const crdt_tuples &t) {
     return !((((uintptr_t)t.key | (uintptr_t)t.ts) & 7) | ((uintptr_t)t.rep & 3));
 }
 
-template <bool LWW>
+static bool bytes_overlap(const void *a, size_t an, const void *b, size_t bn) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return an && bn && x < y + bn && y < x + an;
+}
+// p[0 .. bytes) against the four columns of n tuples
+static bool overlaps_tuples(const void *p, size_t bytes, const crdt_tuples &t, size_t n) {
+    return bytes_overlap(p, bytes, t.key, n * 8) || bytes_overlap(p, bytes, t.ts, n * 8) ||
+           bytes_overlap(p, bytes, t.rep, n * 4) || bytes_overlap(p, bytes, t.tomb, n);
+}
+
+// WITH_SRC: the _src entry points (src_out: na + nb int64, the source index of every output)
+template <bool LWW, bool WITH_SRC = false>
 static int set_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,
-                     crdt_tuples *out, uint64_t *out_count) {
+                     crdt_tuples *out, uint64_t *out_count, int64_t *src_out = nullptr) {
     int rc = bind(ctx);
     if (rc) return rc;
     if (!out_count || !tuples_ok(out)) return CRDT_E_INVAL;
     if ((na && !tuples_ok(a)) || (nb && !tuples_ok(b))) return CRDT_E_INVAL;
     if ((na && !dma_aligned(*a)) || (nb && !dma_aligned(*b))) return CRDT_E_INVAL;
+    if (WITH_SRC && na + nb) {
+        if (na + nb >= (1ULL << 62)) return CRDT_E_RANGE;
+        const size_t sb = (na + nb) * 8;
+        if (!src_out || ((uintptr_t)src_out & 7)) return CRDT_E_INVAL;
+        if ((na && overlaps_tuples(src_out, sb, *a, na)) || (nb && overlaps_tuples(src_out, sb, *b, nb)) ||
+            overlaps_tuples(src_out, sb, *out, na + nb))
+            return CRDT_E_INVAL;
+    }
     if (na + nb == 0) {
         hipError_t e = hipMemsetAsync(out_count, 0, sizeof(uint64_t), ctx->stream);
         return e == hipSuccess ? CRDT_OK : hip_fail(ctx, e);
@@ -1171,8 +977,37 @@ static int set_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_
     crdt_tuples empty{nullptr, nullptr, nullptr, nullptr};
     const crdt_tuples &A = na ? *a : empty;
     const crdt_tuples &B = nb ? *b : empty;
-    return LWW ? lww_merge_keyruns(ctx, A, na, B, nb, *out, out_count)
-               : orset_merge_twopass(ctx, A, na, B, nb, *out, out_count);
+    int64_t *src = WITH_SRC ? src_out : nullptr;
+    return LWW ? lww_merge_keyruns(ctx, A, na, B, nb, *out, src, out_count)
+               : orset_merge_twopass(ctx, A, na, B, nb, *out, src, out_count);
+}
+
+// out_col[i] = the element src[i] names -- a_col[src[i]] (src[i] >= 0) or
+// b_col[-(src[i] + 1)] -- for i < n, n from n_max / n_dev as in setread.hip.
+// One lane per element, grid-stride.  A merge's src is ascending within each
+// side, so a wave's reads of a side fall in a few neighbouring cache lines
+// (near-sequential: no LDS staging would read fewer lines); the stores are
+// coalesced.  An index outside its side is never dereferenced: the element
+// keeps its value and CRDT_DEV_RANGE is raised.
+template <typename E>
+__global__ __launch_bounds__(256) void k_src_gather(const int64_t *__restrict__ src, uint64_t n_max,
+                                                    const uint64_t *__restrict__ n_dev, const E *__restrict__ a,
+                                                    uint64_t na, const E *__restrict__ b, uint64_t nb,
+                                                    E *__restrict__ out, uint32_t *__restrict__ err) {
+    const uint64_t n = n_dev ? *n_dev : n_max;
+    if (n > n_max) {                                     // (a plan miss's ~0 included) nothing touched
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, CRDT_DEV_RANGE);
+        return;
+    }
+    bool bad = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const int64_t s = src[i];
+        const bool on_a = s >= 0;
+        const uint64_t j = on_a ? (uint64_t)s : ~(uint64_t)s;   // -(s + 1)
+        if (j < (on_a ? na : nb)) out[i] = (on_a ? a : b)[j];
+        else bad = true;
+    }
+    if (bad) atomicOr(err, CRDT_DEV_RANGE);
 }
 
 }  // namespace crdt
@@ -1187,6 +1022,51 @@ extern "C" int crdt_lww_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, co
 extern "C" int crdt_orset_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,
                                 crdt_tuples *out, uint64_t *out_count_dev) {
     return set_merge<false>(ctx, a, na, b, nb, out, out_count_dev);
+}
+
+extern "C" int crdt_lww_merge_src(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,
+                                  crdt_tuples *out, int64_t *src_out_dev, uint64_t *out_count_dev) {
+    return set_merge<true, true>(ctx, a, na, b, nb, out, out_count_dev, src_out_dev);
+}
+
+extern "C" int crdt_orset_merge_src(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,
+                                    crdt_tuples *out, int64_t *src_out_dev, uint64_t *out_count_dev) {
+    return set_merge<false, true>(ctx, a, na, b, nb, out, out_count_dev, src_out_dev);
+}
+
+extern "C" int crdt_src_gather(crdt_ctx *ctx, const int64_t *src_dev, size_t n_max, const uint64_t *n_dev,
+                               const void *a_col_dev, size_t na, const void *b_col_dev, size_t nb, void *out_col_dev,
+                               size_t elem_size) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const size_t es = elem_size;
+    if (es != 1 && es != 2 && es != 4 && es != 8 && es != 16) return CRDT_E_INVAL;
+    if (n_max >= (1ULL << 62) || na >= (1ULL << 59) || nb >= (1ULL << 59)) return CRDT_E_RANGE;
+    if (n_max == 0) return CRDT_OK;
+    if (!src_dev || !out_col_dev || (na && !a_col_dev) || (nb && !b_col_dev)) return CRDT_E_INVAL;
+    if (((uintptr_t)src_dev & 7) || ((uintptr_t)n_dev & 7) ||
+        (((uintptr_t)out_col_dev | (uintptr_t)a_col_dev | (uintptr_t)b_col_dev) & (es - 1)))
+        return CRDT_E_INVAL;
+    if (mul_overflows(n_max, es)) return CRDT_E_RANGE;
+    const size_t ob = n_max * es;
+    if (bytes_overlap(out_col_dev, ob, src_dev, n_max * 8) || bytes_overlap(out_col_dev, ob, a_col_dev, na * es) ||
+        bytes_overlap(out_col_dev, ob, b_col_dev, nb * es))
+        return CRDT_E_INVAL;
+    const unsigned g = grid_for(n_max, 256, (unsigned)ctx->num_cus * 8);
+    const hipStream_t s = ctx->stream;
+    uint32_t *err = ctx->dev_status;
+#define GATHER(E)                                                                                                   \
+    k_src_gather<E><<<g, 256, 0, s>>>(src_dev, n_max, n_dev, (const E *)a_col_dev, na, (const E *)b_col_dev, nb, \
+                                      (E *)out_col_dev, err)
+    switch (es) {
+    case 1: GATHER(uint8_t); break;
+    case 2: GATHER(uint16_t); break;
+    case 4: GATHER(uint32_t); break;
+    case 8: GATHER(uint64_t); break;
+    default: GATHER(uint4); break;                       // 16 bytes: one dwordx4 load and store per element
+    }
+#undef GATHER
+    return check_launch(ctx);
 }
 
 extern "C" int crdt_tuples_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,

@@ -246,6 +246,89 @@ class Engine:
         """OR-Set merge: union of tags, tombstones OR-ed."""
         return self._set_merge("crdt_orset_merge", a, b, out, count, trim)
 
+    # -- merges that carry a payload: every output's source index, and the
+    #    gather of value columns by it (crdt_*_merge_src / crdt_src_gather)
+    def _set_merge_src(self, fn: str, a: TupleSet, b: TupleSet, out: TupleSet | None, src: torch.Tensor | None):
+        na, nb = len(a), len(b)
+        out = TupleSet.empty(max(na + nb, 1), self.device) if out is None else out
+        src = torch.empty(max(na + nb, 1), dtype=torch.int64, device=self.device) if src is None else src
+        count = torch.empty(1, dtype=torch.int64, device=self.device)
+        for s in (a, b, out):
+            self._check(s.key, s.ts, itemsize=8)
+            self._check(s.rep, itemsize=4)
+            self._check(s.tomb, itemsize=1)
+        self._check(src, itemsize=8)
+        if src.dtype != torch.int64 or src.numel() < na + nb or len(out) < na + nb:
+            raise ValueError("merge_src: out and src (int64) must hold len(a) + len(b) entries")
+        ca, cb, co = a.c(), b.c(), out.c()
+        self._call(fn, C.byref(ca), na, C.byref(cb), nb, C.byref(co), src.data_ptr(), count.data_ptr())
+        return out, count, src
+
+    def lww_merge_src(self, a: TupleSet, b: TupleSet, out: TupleSet | None = None, src: torch.Tensor | None = None):
+        """:meth:`lww_merge` that also says where every output tuple came
+        from: returns (out, count, src), device-resident, no synchronisation
+        -- out / src of capacity len(a) + len(b), their first ``count``
+        entries valid.  src[i] >= 0: out[i] is a[src[i]]; src[i] < 0: it is
+        b[-(src[i] + 1)] -- the first copy, in merged order, of the key's
+        maximal (ts, rep) tag."""
+        return self._set_merge_src("crdt_lww_merge_src", a, b, out, src)
+
+    def orset_merge_src(self, a: TupleSet, b: TupleSet, out: TupleSet | None = None, src: torch.Tensor | None = None):
+        """:meth:`orset_merge` with every output's source index (see
+        :meth:`lww_merge_src`): the first copy of the tag in merged order;
+        out.tomb stays the OR over all copies."""
+        return self._set_merge_src("crdt_orset_merge_src", a, b, out, src)
+
+    def gather_src(self, src: torch.Tensor, a_col: torch.Tensor, b_col: torch.Tensor,
+                   n_dev: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[i] = a_col[src[i]] if src[i] >= 0 else b_col[-(src[i] + 1)]
+        for the first ``n_dev`` (int64[1] on the device, e.g. the merge's
+        count; default: all) entries of ``src``: one payload column moved by
+        a merge's source indices, no synchronisation.  The columns share one
+        dtype; an element is one entry of a 1-D column, or one row of a
+        contiguous 2-D column whose rows are 1, 2, 4, 8 or 16 bytes.  An
+        index outside its side leaves its output element alone and raises
+        CRDT_DEV_RANGE in :meth:`device_status`, as does n_dev > len(src)."""
+        if a_col.dtype != b_col.dtype or a_col.dim() != b_col.dim() or a_col.dim() not in (1, 2):
+            raise ValueError("gather_src: a_col and b_col must share one dtype and be 1-D (or [n, w] rows)")
+        if a_col.dim() == 2 and a_col.shape[1] != b_col.shape[1]:
+            raise ValueError("gather_src: a_col and b_col rows differ in width")
+        row = tuple(a_col.shape[1:])
+        es = a_col.element_size() * (row[0] if row else 1)
+        if es not in (1, 2, 4, 8, 16):
+            raise ValueError(f"gather_src: {es}-byte elements (1, 2, 4, 8 or 16)")
+        n = src.numel()
+        out = torch.empty((max(n, 1),) + row, dtype=a_col.dtype, device=self.device) if out is None else out
+        self._check(src, itemsize=8)
+        self._check(a_col, b_col, out)
+        if src.dtype != torch.int64 or src.dim() != 1:
+            raise ValueError("gather_src: src must be a 1-D int64 tensor")
+        if out.dtype != a_col.dtype or tuple(out.shape[1:]) != row or out.shape[0] < n:
+            raise ValueError("gather_src: out must hold len(src) elements of the columns' dtype")
+        if n_dev is not None:
+            self._check(n_dev, itemsize=8)
+        self._call("crdt_src_gather", _ptr(src), n, _ptr(n_dev), _ptr(a_col), a_col.shape[0], _ptr(b_col),
+                   b_col.shape[0], _ptr(out), es)
+        return out
+
+    def _map_merge(self, merge, a: TupleSet, a_val: torch.Tensor, b: TupleSet, b_val: torch.Tensor):
+        if a_val.shape[0] != len(a) or b_val.shape[0] != len(b):
+            raise ValueError("map_merge: one value per tuple on each side")
+        out, count, src = merge(a, b)
+        return out, self.gather_src(src, a_val, b_val, n_dev=count), count
+
+    def lww_map_merge(self, a: TupleSet, a_val: torch.Tensor, b: TupleSet, b_val: torch.Tensor):
+        """LWW-Map merge: the tuples of :meth:`lww_merge` and, beside each,
+        the value its winning input tuple carried (a_val[i] belongs to a's
+        tuple i).  Returns (out, out_val, count), device-resident: the merge,
+        then one gather chained off its device count -- no read-back."""
+        return self._map_merge(self.lww_merge_src, a, a_val, b, b_val)
+
+    def orset_map_merge(self, a: TupleSet, a_val: torch.Tensor, b: TupleSet, b_val: torch.Tensor):
+        """OR-Map merge: :meth:`orset_merge` with the payload of each tag's
+        first copy in merged order (see :meth:`lww_map_merge`)."""
+        return self._map_merge(self.orset_merge_src, a, a_val, b, b_val)
+
     def lww_merge_unsorted(self, a: TupleSet, b: TupleSet, out: TupleSet | None = None,
                            count: torch.Tensor | None = None, trim: bool = True):
         """LWW merge of UNSORTED sides (D2): one fused device sort + dedup;

@@ -211,6 +211,49 @@ func SetDeltaCount(lww bool, src *C.crdt_tuples, nsMax int, nsDev *C.uint64_t, d
 	return SetDelta(lww, src, nsMax, nsDev, dst, ndMax, ndDev, nil, countDev)
 }
 
+// LWWMergeSrc: crdt_lww_merge of two sorted set states in HBM that also names,
+// for every output tuple, the input tuple it is -- srcOutDev[i] >= 0: a's tuple
+// of that index; < 0: b's tuple j as -(j+1) -- the first element in merged
+// order (a's copies of an equal tag before b's) carrying the key's maximal
+// (ts, rep).  What a host that keeps a value beside each key needs (the
+// reference Puts the value with its key, main.go:60-64 and :187): GatherSrc
+// then moves the value columns.  out and srcOutDev hold na + nb entries; out
+// and countDev are the plain merge's bit for bit.  Enqueued.
+func LWWMergeSrc(a *C.crdt_tuples, na int, b *C.crdt_tuples, nb int, out *C.crdt_tuples, srcOutDev *C.int64_t,
+	countDev *C.uint64_t) error {
+	if na < 0 || nb < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_lww_merge_src(gpuCtx, a, C.size_t(na), b, C.size_t(nb), out, srcOutDev, countDev))
+}
+
+// ORSetMergeSrc: crdt_orset_merge likewise; the source of a tag's output is
+// the tag's first element in merged order (its tomb stays the OR over all
+// copies, so it may be 1 where the source's is 0).
+func ORSetMergeSrc(a *C.crdt_tuples, na int, b *C.crdt_tuples, nb int, out *C.crdt_tuples, srcOutDev *C.int64_t,
+	countDev *C.uint64_t) error {
+	if na < 0 || nb < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_orset_merge_src(gpuCtx, a, C.size_t(na), b, C.size_t(nb), out, srcOutDev, countDev))
+}
+
+// GatherSrc: outColDev[i] = aColDev[src[i]] (src[i] >= 0) or bColDev[-(src[i]+1)]
+// for the first *nDev (nil: nMax) source indices, elements of elemSize 1, 2,
+// 4, 8 or 16 bytes: one payload column moved by a merge's source indices, one
+// call per column.  Pass the merge's countDev as nDev: no read-back between
+// the merge and the gather.  An index outside its side leaves its output
+// element as it was and raises CRDT_DEV_RANGE, as does *nDev > nMax (nothing
+// touched).  Enqueued: crdt_ctx_sync before reading.
+func GatherSrc(srcDev *C.int64_t, nMax int, nDev *C.uint64_t, aColDev unsafe.Pointer, na int, bColDev unsafe.Pointer,
+	nb int, outColDev unsafe.Pointer, elemSize int) error {
+	if nMax < 0 || na < 0 || nb < 0 || elemSize < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_src_gather(gpuCtx, srcDev, C.size_t(nMax), nDev, aColDev, C.size_t(na), bColDev, C.size_t(nb),
+		outColDev, C.size_t(elemSize)))
+}
+
 // RCCLInfo: which RCCL the process runs (for the service's logs / metrics).
 func RCCLInfo() (int, string) {
 	var v C.int

@@ -177,6 +177,48 @@ int crdt_lww_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tu
 /* OR-Set: union of unique tags (key, ts, rep); tomb OR-ed over equal tags. */
 int crdt_orset_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b,
                      size_t nb, crdt_tuples *out, uint64_t *out_count_dev);
+/* ---- merges that carry a payload: where every output tuple came from (the
+ * reference's state is key -> value, Diff.Put of a value with its key at
+ * main.go:60-64 and :187; a tuple has no value column, so the merge names
+ * the input tuple and crdt_src_gather moves any number of value columns).
+ * crdt_lww_merge_src / crdt_orset_merge_src write out and *out_count_dev bit
+ * for bit as crdt_lww_merge / crdt_orset_merge do for the same inputs, under
+ * the same preconditions, alignment rules, error codes and (no)
+ * synchronisation, and also src_out_dev[i] = the source of out[i], encoded as
+ * crdt_refmerge_out.src: >= 0 an index into a; < 0 b's index j as -(j + 1).
+ * src_out_dev holds >= na + nb int64, 8-byte aligned; entries at or past the
+ * count are unspecified.  Which copy is the source -- merged order is the
+ * stable merge of a and b by (key, ts, rep): a's copies of an equal tag before
+ * b's, each side in its input order:
+ *   LWW    : the first element in merged order that carries the key's maximal
+ *            (ts, rep); all four output fields are that element's.
+ *   OR-Set : the first element in merged order of the tag; key, ts and rep
+ *            are that element's, tomb stays the OR over all copies (it may be
+ *            1 where the source's is 0).
+ * CRDT_E_INVAL besides the plain merges' cases: src_out_dev NULL with na + nb
+ * > 0, misaligned, or overlapping a, b or out. */
+int crdt_lww_merge_src(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,
+                       crdt_tuples *out, int64_t *src_out_dev, uint64_t *out_count_dev);
+int crdt_orset_merge_src(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,
+                         crdt_tuples *out, int64_t *src_out_dev, uint64_t *out_count_dev);
+/* out_col[i] = src[i] >= 0 ? a_col[src[i]] : b_col[-(src[i] + 1)] for i < n,
+ * elements of elem_size in {1, 2, 4, 8, 16} bytes: one payload column moved
+ * by a merge's source indices (one call per column; columns naturally aligned
+ * to elem_size).  n from n_max / n_dev exactly as in crdt_set_elements: NULL
+ * -> n_max; *n_dev <= n_max -> the first *n_dev (pass the merge's
+ * out_count_dev: no read-back between the merge and the gather); *n_dev >
+ * n_max (the ~0 of a plan miss included) -> nothing is touched and
+ * CRDT_DEV_RANGE is raised.  An index outside its side (src >= na, or
+ * -(src + 1) >= nb) is never dereferenced: its output element is left as it
+ * was and CRDT_DEV_RANGE is raised; every other element is still written.
+ * Stream-ordered, no host synchronisation, no workspace (capturable).
+ * CRDT_E_INVAL: a bad elem_size, a NULL src / out_col or a NULL side with a
+ * nonzero length, misalignment (src and n_dev to 8 bytes, the columns to
+ * elem_size), out_col overlapping an input column or src; CRDT_E_RANGE: n_max
+ * >= 2^62 (or a side of 2^59 elements or more).  n_max == 0 launches nothing. */
+int crdt_src_gather(crdt_ctx *ctx, const int64_t *src_dev, size_t n_max, const uint64_t *n_dev,
+                    const void *a_col_dev, size_t na, const void *b_col_dev, size_t nb,
+                    void *out_col_dev, size_t elem_size);
 /* The same two merges on UNSORTED inputs (config D2), as one device sort of
  * both sides together with a side bit between rep and tomb -- composite
  * order (key, ts, rep, side, tomb) is the stable merge of the two sorted
