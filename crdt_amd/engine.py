@@ -474,6 +474,86 @@ class Engine:
                    _ptr(n_dst_dev), None if co is None else C.byref(co), count.data_ptr())
         return count
 
+    # -- tombstone compaction under a causal-stability cut (crdt_set_compact)
+    def set_compact(self, t: TupleSet, lww: bool, cut: torch.Tensor | None, n_dev: torch.Tensor | None = None,
+                    out: TupleSet | None = None, src: torch.Tensor | None = None, count: torch.Tensor | None = None,
+                    with_src: bool = False, trim: bool = False):
+        """merge(t, {}) of the sorted set state ``t`` without its stable dead
+        tuples: a tag (key, ts, rep) is stable iff rep < len(cut) and ts <=
+        cut[rep] (``cut``: int64 storage of uint64 on the device, e.g.
+        :meth:`vclock_stable_cut`; None: no cut, nothing is dropped).  OR-Set
+        drops a stable tag whose copies' tomb-OR is 1, LWW a key whose winner
+        is a stable tombstone.  The caller vouches that every replica holds
+        the tombstones the cut makes stable.  Returns (out, count), or (out,
+        src, count) with ``with_src`` (or a ``src`` tensor): device-resident,
+        no synchronisation -- out / src of capacity len(t), their first
+        ``count`` entries valid, src[i] the index in t of out[i]'s tuple (the
+        first copy of its tag), for :meth:`gather_src`.  ``n_dev`` as in
+        :meth:`set_elements`; with ``trim`` the device status is checked and
+        the sliced results returned."""
+        n = len(t)
+        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
+        if len(out) < n:
+            raise ValueError("set_compact: out holds fewer tuples than t")
+        if src is None and with_src:
+            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        if src is not None:
+            self._check(src, itemsize=8)
+            if src.dtype != torch.int64 or src.numel() < n:
+                raise ValueError("set_compact: src must be int64 and hold len(t) entries")
+        count = self._set_compact(t, lww, cut, n_dev, out, src, count)
+        if trim:
+            self.check_device()
+            k = int(count.item())
+            return (out.slice(k), count) if src is None else (out.slice(k), src[:k], count)
+        return (out, count) if src is None else (out, src, count)
+
+    def set_compact_count(self, t: TupleSet, lww: bool, cut: torch.Tensor | None, n_dev: torch.Tensor | None = None,
+                          count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(compact(t, cut)) alone (int64[1] on the device, no
+        synchronisation): one pass over the tuples, nothing else written."""
+        return self._set_compact(t, lww, cut, n_dev, None, None, count)
+
+    def _set_compact(self, t: TupleSet, lww: bool, cut, n_dev, out, src, count) -> torch.Tensor:
+        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        self._check(count, itemsize=8)
+        for s in (t,) + (() if out is None else (out,)):
+            self._check(s.key, s.ts, itemsize=8)
+            self._check(s.rep, itemsize=4)
+            self._check(s.tomb, itemsize=1)
+        for x in (cut, n_dev):
+            if x is not None:
+                self._check(x, itemsize=8)
+        ct = t.c()
+        co = None if out is None else out.c()
+        self._call("crdt_set_compact", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev), _ptr(cut),
+                   0 if cut is None else cut.numel(), None if co is None else C.byref(co), _ptr(src),
+                   count.data_ptr())
+        return count
+
+    def map_compact(self, t: TupleSet, val: torch.Tensor, lww: bool, cut: torch.Tensor | None):
+        """:meth:`set_compact` of a state that keeps a value beside each
+        tuple (val[i] belongs to t's tuple i): returns (out, out_val, count),
+        device-resident -- the compaction, then one :meth:`gather_src` of
+        ``val`` chained off its device count, no read-back."""
+        if val.shape[0] != len(t):
+            raise ValueError("map_compact: one value per tuple")
+        out, src, count = self.set_compact(t, lww, cut, with_src=True)
+        return out, self.gather_src(src, val, val[:0], n_dev=count), count
+
+    def vclock_stable_cut(self, clocks: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[c] = min over rows of clocks[:, c] (unsigned): the
+        causal-stability cut of a [replicas, nodes] clock population -- what
+        :meth:`set_compact` takes as ``cut``.  No replicas is an error (the
+        minimum over none would make every tombstone droppable)."""
+        rows, nodes = clocks.shape
+        out = torch.empty(nodes, dtype=torch.int64, device=self.device) if out is None else out
+        self._check(clocks, out, itemsize=8)
+        if out.numel() < nodes:
+            raise ValueError("vclock_stable_cut: out holds fewer entries than the clocks have nodes")
+        self._call("crdt_vclock_stable_cut", clocks.data_ptr(), rows, nodes, out.data_ptr())
+        return out
+
     def tuples_merge(self, a: TupleSet, b: TupleSet, out: TupleSet | None = None) -> TupleSet:
         """Stable merge of two sorted tuple arrays, every tuple kept (a's
         copies first on an equal tag): crdt_tuples_merge."""

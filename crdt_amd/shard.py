@@ -478,6 +478,50 @@ class Comm:
         self._call("crdt_shard_allreduce_max_u64", self._ptrs(bufs), bufs[0].numel())
         return bufs
 
+    def stable_cut(self, shards: Sequence[torch.Tensor], outs: Sequence[torch.Tensor] | None = None):
+        """The causal-stability cut of a row-sharded [rows, nodes] clock
+        population: every member's out = the column minimum over ALL members'
+        rows (what ``Engine.set_compact`` takes as its cut).  Each member runs
+        crdt_vclock_stable_cut on its shard; min(x) = ~max(~x), so the
+        complements go through the existing :meth:`allreduce_max_u64` and are
+        complemented back -- no collective of its own.  A member without rows
+        contributes zeros in the complemented domain (the minimum's identity);
+        if no member of this communicator has a row, ValueError (the minimum
+        over no replica would make every tombstone droppable).  The
+        complements are torch ops, so the call synchronises the member
+        streams around them; the outputs are ready when it returns."""
+        if len(shards) != self.members:
+            raise ValueError(f"expected one shard per member ({self.members})")
+        nodes = shards[0].shape[1]
+        if any(s.dim() != 2 or s.shape[1] != nodes for s in shards):
+            raise ValueError("every shard must be [rows, nodes] with one node count")
+        if all(s.shape[0] == 0 for s in shards):
+            raise ValueError("stable_cut: no member holds a row")
+        if outs is None:
+            outs = [torch.empty(nodes, dtype=torch.int64, device=d) for d in self.devices]
+        self._ptrs(outs)
+        for i, (s, o) in enumerate(zip(shards, outs)):
+            if s.shape[0] == 0:
+                o.fill_(-1)                 # ~0 here, 0 once complemented
+                continue
+            if s.device != o.device or not s.is_contiguous() or s.element_size() != 8 or o.numel() != nodes:
+                raise ValueError("stable_cut: shards contiguous 8-byte [rows, nodes], outs of nodes entries")
+            ctx = C.c_void_p()
+            self._call("crdt_shard_member_ctx", i, C.byref(ctx))
+            _lib.call("crdt_vclock_stable_cut", ctx, s.data_ptr(), s.shape[0], nodes, o.data_ptr(), ctx=ctx)
+        self.sync()
+        for o in outs:
+            torch.bitwise_not(o, out=o)
+        for d in set(self.devices):
+            torch.cuda.synchronize(d)
+        self.allreduce_max_u64(outs)
+        self.sync()
+        for o in outs:
+            torch.bitwise_not(o, out=o)
+        for d in set(self.devices):
+            torch.cuda.synchronize(d)
+        return outs
+
     def allreduce(self, bufs: Sequence[torch.Tensor], op: str = "sum"):
         """In-place all-reduce of int64 / int32 tensors (signed), op 'sum' | 'max'."""
         t = {torch.int64: 0, torch.int32: 3}[bufs[0].dtype]

@@ -211,6 +211,50 @@ func SetDeltaCount(lww bool, src *C.crdt_tuples, nsMax int, nsDev *C.uint64_t, d
 	return SetDelta(lww, src, nsMax, nsDev, dst, ndMax, ndDev, nil, countDev)
 }
 
+// StableCut: the causal-stability cut of a [rows x nodes] uint64 vector-clock
+// population in HBM -- outDev[c] = the minimum over the rows of column c, the
+// number of node c's events every replica has seen.  What SetCompact takes as
+// its cut.  rows == 0 is an error (the minimum over no replica is all-ones:
+// every tombstone would be droppable).  Enqueued: crdt_ctx_sync before reading.
+func StableCut(clocksDev *C.uint64_t, rows, nodes int, outDev *C.uint64_t) error {
+	if rows <= 0 || nodes <= 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_vclock_stable_cut(gpuCtx, clocksDev, C.size_t(rows), C.size_t(nodes), outDev))
+}
+
+// SetCompact: the sorted set state t without its stable dead tuples --
+// merge(t, {}) minus every OR-Set tag whose copies' tomb-OR is 1, and every
+// LWW key whose winner is a tombstone, that is stable under the cut: rep <
+// nCut and ts <= cutDev[rep].  The reference's Diff only grows; this is the
+// pass that lets a long-running replica shed tombstones.  The caller vouches
+// that the cut covers the remove as well as the add: every replica already
+// holds the tombstone of every tag the cut makes stable.  The kept tuples go
+// to out in ascending order (capacity nMax), their number to countDev;
+// srcOutDev (nil: not wanted; capacity nMax) receives per output tuple the
+// index in t of the tuple it is (the first copy of its tag), for GatherSrc
+// with bColDev nil.  cutDev nil with nCut 0: no cut, the result is merge(t,
+// {}).  nDev (nil: nMax tuples) chains the call off a merge's device count
+// with no read-back.  Enqueued: crdt_ctx_sync before reading.
+func SetCompact(lww bool, t *C.crdt_tuples, nMax int, nDev *C.uint64_t, cutDev *C.uint64_t, nCut int,
+	out *C.crdt_tuples, srcOutDev *C.int64_t, countDev *C.uint64_t) error {
+	if t == nil || countDev == nil || nMax < 0 || nCut < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	mode := C.int(C.CRDT_SET_ORSET)
+	if lww {
+		mode = C.int(C.CRDT_SET_LWW)
+	}
+	return status(C.crdt_set_compact(gpuCtx, mode, t, C.size_t(nMax), nDev, cutDev, C.size_t(nCut), out, srcOutDev, countDev))
+}
+
+// SetCompactCount: the size of that compaction alone (nothing stored but the
+// count) -- how much a compaction under this cut would free.
+func SetCompactCount(lww bool, t *C.crdt_tuples, nMax int, nDev *C.uint64_t, cutDev *C.uint64_t, nCut int,
+	countDev *C.uint64_t) error {
+	return SetCompact(lww, t, nMax, nDev, cutDev, nCut, nil, nil, countDev)
+}
+
 // LWWMergeSrc: crdt_lww_merge of two sorted set states in HBM that also names,
 // for every output tuple, the input tuple it is -- srcOutDev[i] >= 0: a's tuple
 // of that index; < 0: b's tuple j as -(j+1) -- the first element in merged

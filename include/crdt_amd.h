@@ -149,6 +149,17 @@ typedef enum crdt_vc_class {
     CRDT_VC_CONCURRENT = 3  /* neither dominates        */
 } crdt_vc_class;
 /* Join of vector clocks is the elementwise max: crdt_gcounter_join. */
+/* The causal-stability cut of a population of [rows x nodes] uint64 clocks:
+ * out[c] = min_r clocks[r][c] (unsigned) -- the number of node c's events that
+ * every replica has seen; what crdt_set_compact takes as its cut.  The
+ * column-min twin of crdt_gcounter_fold (same two paths: nodes a power of two
+ * in [2, 512] on a 16-byte aligned base streams 16-byte loads, anything else
+ * takes the generic kernel).  rows == 0 is CRDT_E_INVAL: the minimum over no
+ * replica is all-ones, a cut under which every tombstone could go.  nodes ==
+ * 0, a NULL pointer or rows * nodes overflowing: CRDT_E_INVAL.  Stream-ordered,
+ * no host synchronisation (capturable after crdt_ctx_reserve). */
+int crdt_vclock_stable_cut(crdt_ctx *ctx, const uint64_t *clocks_dev, size_t rows, size_t nodes,
+                           uint64_t *out_dev);
 /* cls[p] = classify(a[p], b[p]) for [pairs x nodes] uint64 clocks.  With
  * nodes == 1 this is the sign of Int64Comparator (main.go:106) on unsigned
  * values, mapped EQUAL/BEFORE/AFTER. */
@@ -336,6 +347,58 @@ int crdt_u64_contains(crdt_ctx *ctx, const uint64_t *sorted_dev, size_t n_max, c
 int crdt_set_delta(crdt_ctx *ctx, int mode, const crdt_tuples *src, size_t ns_max, const uint64_t *ns_dev,
                    const crdt_tuples *dst, size_t nd_max, const uint64_t *nd_dev, const crdt_tuples *out,
                    uint64_t *count_dev);
+/* ---- tombstone compaction under a causal-stability cut (no reference
+ * counterpart: the reference's Diff only grows).  The merges keep tombstoned
+ * LWW winners and every OR-Set tag ever seen; this call drops the dead tuples
+ * that every replica is known to hold.
+ * Stable: for a cut cut_dev[0 .. n_cut) of uint64, a tag (key, ts, rep) is
+ * stable iff rep < n_cut and ts <= cut[rep] (unsigned compare).  A rep at or
+ * past n_cut is never stable; n_cut == 0 (cut_dev may then be NULL): nothing is.
+ * compact(t, cut), t sorted ascending by (key, ts, rep), copies of one tag in
+ * any order, is merge(t, {}) with the stable dead tuples removed:
+ *   OR-Set : per distinct tag, tomb = the OR over its copies; the tag is
+ *            dropped iff that OR is 1 and the tag is stable, otherwise written
+ *            once with that OR.
+ *   LWW    : per distinct key, the winner is the maximal (ts, rep) tag with the
+ *            tomb of that tag's first copy (crdt_lww_merge's winner); the key
+ *            is dropped iff the winner's tomb is 1 and the winner is stable,
+ *            otherwise the winner is written.
+ * out receives the kept tuples in ascending tuple order, *count_dev (device
+ * uint64) their number: a sorted state the merges, reads and deltas accept.
+ * compact(t, no cut) == merge(t, {}) bit for bit; crdt_set_elements of the
+ * result equals that of t for every cut; compact is idempotent; a cut that is
+ * column-wise >= another yields a subsequence of the other's result.
+ * THE CALLER'S OBLIGATION (not enforced): the cut must cover the REMOVE as
+ * well as the add -- every replica already holds the tombstone of every tag
+ * the cut makes stable (e.g. ts counts rep's events, add and remove alike, and
+ * the cut is crdt_vclock_stable_cut of the replicas' clocks).  A dropped
+ * tombstone that some replica has not seen lets that replica's live copy
+ * resurrect the element at the next merge.
+ * src_out_dev (may be NULL): per output tuple the index into t of the tuple it
+ * is -- LWW: the first copy of the winner tag; OR-Set: the first copy of the
+ * tag (its tomb may be 0 where the output's OR is 1) -- the copies
+ * crdt_*_merge_src(t, {}) names, encoded as that call's a-side (>= 0), so
+ * crdt_src_gather(src, n_max, count_dev, col, n, NULL, 0, out_col, elem)
+ * compacts a value column with no read-back.
+ * out may be NULL: the count alone (no bitmaps, no offsets, nothing stored but
+ * *count_dev); src_out_dev must then be NULL too.
+ * n_dev follows crdt_set_elements' n_dev: NULL -> n_max tuples; *n_dev <= n_max
+ * -> the first *n_dev; *n_dev > n_max -> no tuple is touched, nothing is
+ * written to out or src_out_dev, *count_dev = ~0 and CRDT_DEV_RANGE is raised.
+ * No kernel reads a tuple at or past min(*n_dev, n_max) or before 0 (the write
+ * pass checks every position of its bitmaps against that length before it
+ * loads), nor cut_dev at or past n_cut.  Stream-ordered, no host
+ * synchronisation (capturable after crdt_ctx_reserve).  out holds >= n_max
+ * tuples, src_out_dev >= n_max int64; neither may overlap t, cut_dev or the
+ * other.  CRDT_E_INVAL: NULL ctx / t / count_dev, bad mode, NULL fields of t
+ * or out with n_max > 0, key / ts / rep of t or out not naturally aligned,
+ * cut_dev NULL with n_cut > 0, cut_dev or src_out_dev not 8-byte aligned,
+ * src_out_dev without out, an overlap as above; CRDT_E_RANGE: n_max >= 2^62,
+ * n_cut >= 2^32, or more tiles than a launch holds.  n_max == 0 launches
+ * nothing but the count store. */
+int crdt_set_compact(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
+                     const uint64_t *cut_dev, size_t n_cut, const crdt_tuples *out, int64_t *src_out_dev,
+                     uint64_t *count_dev);
 /* Sortedness check (host-facing validation): *bad_dev = number of adjacent
  * pairs with t[i] > t[i+1]. */
 int crdt_tuples_count_unsorted(crdt_ctx *ctx, const crdt_tuples *t, size_t n,
