@@ -30,6 +30,7 @@
 // memory-side round trip across the 8 XCDs' non-coherent L2s; the extra
 // read of the upsweep costs less than those chains.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 
 #include "scan.hpp"
@@ -3171,6 +3172,13 @@ struct PlanBlob {
 };
 constexpr uint32_t kPlanMagic = 0x43524450u;     // "CRDP"
 static_assert(sizeof(PlanBlob) <= sizeof(crdt_set_plan), "crdt_set_plan holds the plan");
+// tests/d2_util.py (blob_shape) reads the plan's shape out of the blob at these offsets
+static_assert(offsetof(PlanBlob, mode) == 4 && offsetof(PlanBlob, na) == 8 && offsetof(PlanBlob, nb) == 16 &&
+                  offsetof(PlanBlob, h) == 24 && offsetof(SortPlan, bk) == 24 && offsetof(SortPlan, bt) == 28 &&
+                  offsetof(SortPlan, br) == 32 && offsetof(SortPlan, W) == 36 && offsetof(SortPlan, P) == 40 &&
+                  offsetof(SortPlan, words) == 44 && offsetof(SortPlan, b0) == 48 && offsetof(SortPlan, s0) == 52 &&
+                  offsetof(SortPlan, tl) == 56 && offsetof(SortPlan, tw) == 60,
+              "tests/d2_util.py reads these words of the plan blob");
 
 static int set_merge_plan(crdt_ctx *ctx, int mode, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,
                           uint32_t widen, crdt_set_plan *plan) {
