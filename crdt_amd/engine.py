@@ -541,6 +541,121 @@ class Engine:
         out, src, count = self.set_compact(t, lww, cut, with_src=True)
         return out, self.gather_src(src, val, val[:0], n_dev=count), count
 
+    # -- range digests: where two states differ, without shipping either
+    #    (crdt_set_digest / crdt_set_digest_diff / crdt_set_select)
+    def _check_tuples(self, *sets: TupleSet) -> None:
+        for s in sets:
+            self._check(s.key, s.ts, itemsize=8)
+            self._check(s.rep, itemsize=4)
+            self._check(s.tomb, itemsize=1)
+
+    def set_digest(self, t: TupleSet, lww: bool, splitters: torch.Tensor | None, n_dev: torch.Tensor | None = None,
+                   hash_out: torch.Tensor | None = None, count_out: torch.Tensor | None = None):
+        """One order-independent fingerprint per key range of the sorted set
+        state ``t``: returns (hash, count), int64 storage of uint64 on the
+        device, len(splitters) + 1 entries each, no synchronisation.
+        ``splitters`` (ascending uint64 in int64 storage on the device; None
+        or empty: one bucket) put a key into bucket #{j : splitters[j] <=
+        key}; hash[b] is the wrapping sum over the tuples of merge(t, {}) in b
+        of sm(sm(sm(key) ^ ts) ^ (rep << 1 | tomb)), sm =
+        :func:`crdt_amd.synth.splitmix64`, count[b] their number.  Equal
+        canonical tuples in a bucket give equal entries, whatever the copies
+        and their order.  ``n_dev`` as in :meth:`set_elements`; a value over
+        len(t) leaves every entry 2^64 - 1 and raises CRDT_DEV_RANGE."""
+        m = 0 if splitters is None else splitters.numel()
+        hash_out = torch.empty(m + 1, dtype=torch.int64, device=self.device) if hash_out is None else hash_out
+        count_out = torch.empty(m + 1, dtype=torch.int64, device=self.device) if count_out is None else count_out
+        self._check_tuples(t)
+        self._check(hash_out, count_out, itemsize=8)
+        if hash_out.numel() < m + 1 or count_out.numel() < m + 1:
+            raise ValueError("set_digest: the outputs must hold len(splitters) + 1 entries")
+        for x in (splitters, n_dev):
+            if x is not None:
+                self._check(x, itemsize=8)
+        ct = t.c()
+        self._call("crdt_set_digest", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev),
+                   _ptr(splitters) if m else None, m, hash_out.data_ptr(), count_out.data_ptr())
+        return hash_out, count_out
+
+    def digest_diff(self, da, db, flags: torch.Tensor | None = None, n_diff: torch.Tensor | None = None):
+        """Which buckets of two :meth:`set_digest` results (hash, count)
+        differ: returns (flags, n_diff) -- uint8[buckets], 1 where the hashes
+        or the counts differ or either digest is poisoned, and their number
+        (int64[1]), on the device, no synchronisation.  The digests may come
+        from another replica; both must be over the same splitters."""
+        (ha, ca), (hb, cb) = da, db
+        nb = ha.numel()
+        if not (ca.numel() == hb.numel() == cb.numel() == nb):
+            raise ValueError("digest_diff: the four arrays differ in length")
+        flags = torch.empty(max(nb, 1), dtype=torch.uint8, device=self.device) if flags is None else flags
+        n_diff = torch.empty(1, dtype=torch.int64, device=self.device) if n_diff is None else n_diff
+        self._check(ha, ca, hb, cb, n_diff, itemsize=8)
+        self._check(flags, itemsize=1)
+        if flags.numel() < nb:
+            raise ValueError("digest_diff: flags holds fewer entries than the digests have buckets")
+        self._call("crdt_set_digest_diff", _ptr(ha), _ptr(ca), _ptr(hb), _ptr(cb), nb, _ptr(flags), _ptr(n_diff))
+        return flags[:nb], n_diff
+
+    def set_select(self, t: TupleSet, lww: bool, splitters: torch.Tensor | None, flags: torch.Tensor,
+                   n_dev: torch.Tensor | None = None, out: TupleSet | None = None, src: torch.Tensor | None = None,
+                   count: torch.Tensor | None = None, with_src: bool = False, trim: bool = False):
+        """The tuples of merge(t, {}) whose key falls into a bucket with
+        ``flags[b] != 0`` (uint8[len(splitters) + 1], e.g.
+        :meth:`digest_diff`'s), ascending: what a replica ships for the
+        differing ranges.  Returns (out, count), or (out, src, count) with
+        ``with_src`` (or a ``src`` tensor), as :meth:`set_compact` does."""
+        n = len(t)
+        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
+        if len(out) < n:
+            raise ValueError("set_select: out holds fewer tuples than t")
+        if src is None and with_src:
+            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        if src is not None:
+            self._check(src, itemsize=8)
+            if src.dtype != torch.int64 or src.numel() < n:
+                raise ValueError("set_select: src must be int64 and hold len(t) entries")
+        count = self._set_select(t, lww, splitters, flags, n_dev, out, src, count)
+        if trim:
+            self.check_device()
+            k = int(count.item())
+            return (out.slice(k), count) if src is None else (out.slice(k), src[:k], count)
+        return (out, count) if src is None else (out, src, count)
+
+    def set_select_count(self, t: TupleSet, lww: bool, splitters: torch.Tensor | None, flags: torch.Tensor,
+                         n_dev: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(:meth:`set_select`) alone (int64[1] on the device, no
+        synchronisation): how much the flagged ranges would ship."""
+        return self._set_select(t, lww, splitters, flags, n_dev, None, None, count)
+
+    def _set_select(self, t: TupleSet, lww: bool, splitters, flags, n_dev, out, src, count) -> torch.Tensor:
+        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        m = 0 if splitters is None else splitters.numel()
+        self._check(count, itemsize=8)
+        self._check(flags, itemsize=1)
+        if flags.numel() < m + 1:
+            raise ValueError("set_select: flags must hold len(splitters) + 1 entries")
+        self._check_tuples(*((t,) + (() if out is None else (out,))))
+        for x in (splitters, n_dev):
+            if x is not None:
+                self._check(x, itemsize=8)
+        ct = t.c()
+        co = None if out is None else out.c()
+        self._call("crdt_set_select", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev),
+                   _ptr(splitters) if m else None, m, _ptr(flags), None if co is None else C.byref(co), _ptr(src),
+                   count.data_ptr())
+        return count
+
+    def map_select(self, t: TupleSet, val: torch.Tensor, lww: bool, splitters: torch.Tensor | None,
+                   flags: torch.Tensor):
+        """:meth:`set_select` of a state that keeps a value beside each tuple
+        (val[i] belongs to t's tuple i): returns (out, out_val, count),
+        device-resident -- the selection, then one :meth:`gather_src` of
+        ``val`` chained off its device count, no read-back."""
+        if val.shape[0] != len(t):
+            raise ValueError("map_select: one value per tuple")
+        out, src, count = self.set_select(t, lww, splitters, flags, with_src=True)
+        return out, self.gather_src(src, val, val[:0], n_dev=count), count
+
     def vclock_stable_cut(self, clocks: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """out[c] = min over rows of clocks[:, c] (unsigned): the
         causal-stability cut of a [replicas, nodes] clock population -- what

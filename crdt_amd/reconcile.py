@@ -1,0 +1,96 @@
+"""Range-based reconciliation of two set replicas.
+
+Two replicas that do not share a memory learn where they differ from small
+per-range fingerprints instead of each other's state: both cut the key space
+with the same splitters, digest their state per bucket
+(:meth:`Engine.set_digest`, 16 bytes a bucket), exchange the digests, flag the
+buckets that differ (:meth:`Engine.digest_diff`) and ship only those
+(:meth:`Engine.set_select`).  The reference's gossip pull ships the entire
+Diff every round (main.go:153-170, :245-256).
+
+Everything here runs in the library's HIP kernels; torch allocates, indexes
+the splitter keys and fills buffers.
+"""
+from __future__ import annotations
+
+import torch
+
+from .engine import Engine, TupleSet
+
+
+def key_splitters(t: TupleSet, m: int) -> torch.Tensor:
+    """``m`` splitters for about equally filled buckets of the sorted state
+    ``t``: every ceil(n / (m + 1))-th key, t.key[step], t.key[2 step], ...
+    (indices past the end take the last key; duplicates are allowed and give
+    empty buckets).  An int64-storage device tensor, ascending as unsigned
+    because t is sorted.  An empty ``t`` gives all-zero splitters."""
+    if m < 0:
+        raise ValueError("key_splitters: m must be >= 0")
+    n = len(t)
+    if n == 0 or m == 0:
+        return torch.zeros(m, dtype=torch.int64, device=t.key.device)
+    step = -(-n // (m + 1))
+    idx = torch.arange(1, m + 1, dtype=torch.int64, device=t.key.device) * step
+    return t.key[idx.clamp_(max=n - 1)].contiguous()
+
+
+def _ship_and_merge(eng: Engine, dst: TupleSet, src: TupleSet, lww: bool, splitters, flags):
+    """merge(dst, sel(src)) with no read-back of the selection's length.
+
+    The merges take their sides' lengths from the host, the selection's is on
+    the device.  So the selection buffer is first filled with copies of src's
+    last tuple and merged at its whole capacity: the copies sort at or after
+    every selected tuple, and they change nothing -- the tuple's bucket is
+    either flagged (its tag is then in the selection, canonical copy first) or
+    it is not (dst then holds the same canonical tuple there, and dst, the
+    left operand, wins ties; an OR-Set tomb is OR-ed with one it already
+    includes).  Between real replicas the receiver knows the length from the
+    transfer and merges the shipped prefix alone."""
+    cap = len(src)
+    sel = TupleSet.empty(max(cap, 1), eng.device)
+    if cap:
+        for f, s in ((sel.key, src.key), (sel.ts, src.ts), (sel.rep, src.rep), (sel.tomb, src.tomb)):
+            f.copy_(s[cap - 1:cap].expand(f.shape[0]))
+    _, shipped = eng.set_select(src, lww, splitters, flags, out=sel)
+    merge = eng.lww_merge if lww else eng.orset_merge
+    merged, count = merge(dst, sel.slice(cap), trim=False)
+    return merged, count, shipped
+
+
+def reconcile_round(eng: Engine, A: TupleSet, B: TupleSet, lww: bool, splitters: torch.Tensor | None):
+    """One reconciliation round between the sorted set states ``A`` and
+    ``B``, both on ``eng``'s device, standing in for two replicas: each side's
+    digest over ``splitters``, the diff of the two, each side's selection of
+    the flagged buckets, and merge(A, sel(B)) / merge(B, sel(A)).  Everything
+    is enqueued on the stream with no synchronisation and no read-back.
+
+    Returns ``((MA, ca), (MB, cb), flags, (ship_a, ship_b))``: the merged
+    states (TupleSets of capacity len(A) + len(B), their first ``ca`` /
+    ``cb`` tuples valid, int64[1] device counts), the uint8 flags of the
+    buckets that differed, and the numbers of tuples A and B had to ship
+    (int64[1] on the device).  MA equals merge(A, B) and MB merge(B, A) with
+    probability about 1 - 2^-64 per differing bucket; the digest is a
+    checksum, not a defence against an adversary.
+
+    What crosses the wire between real replicas is the digests (16 bytes a
+    bucket) and the selections.  A host that wants to ship less recurses
+    before it selects: finer splitters inside the flagged ranges only ::
+
+        sp = key_splitters(A, 255)
+        flags, n_diff = eng.digest_diff(eng.set_digest(A, lww, sp), eng.set_digest(B, lww, sp))
+        if int(n_diff.item()):
+            # bucket b covers keys [sp[b - 1], sp[b]); cut each flagged one finer
+            a_part, _ = eng.set_select(A, lww, sp, flags, trim=True)   # or the peer's digest of
+            fine = key_splitters(a_part, 4095)                         # its own flagged ranges
+            fine = torch.cat([sp, fine]).sort().values                 # (keys >= 2^63: sort as unsigned)
+            (MA, ca), (MB, cb), flags2, shipped = reconcile_round(eng, A, B, lww, fine)
+
+    Unflagged coarse buckets stay unflagged under the finer cut (their
+    sub-buckets agree too), so only the differing sub-ranges ship.
+    """
+    da = eng.set_digest(A, lww, splitters)
+    db = eng.set_digest(B, lww, splitters)
+    flags, _ = eng.digest_diff(da, db)
+    ma, ca, ship_b = _ship_and_merge(eng, A, B, lww, splitters, flags)
+    mb, cb, ship_a = _ship_and_merge(eng, B, A, lww, splitters, flags)
+    return (ma, ca), (mb, cb), flags, (ship_a, ship_b)

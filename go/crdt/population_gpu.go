@@ -255,6 +255,59 @@ func SetCompactCount(lww bool, t *C.crdt_tuples, nMax int, nDev *C.uint64_t, cut
 	return SetCompact(lww, t, nMax, nDev, cutDev, nCut, nil, nil, countDev)
 }
 
+// SetDigest: one order-independent fingerprint per key range of the sorted set
+// state t -- hashOutDev[b] = the wrapping sum of the tuple hash over the
+// tuples of merge(t, {}) whose key falls into bucket b, countOutDev[b] their
+// number, for the m + 1 buckets the ascending splittersDev cut the key space
+// into (bucket(key) = the number of splitters <= key; m == 0 with a nil
+// splittersDev: one bucket).  Two replicas exchange these 16 bytes a range
+// instead of their state (the reference's pull ships the entire Diff,
+// main.go:153-170, :245-256), SetDigestDiff flags the ranges that differ and
+// SetSelect ships those alone.  The tuple hash is spelt out in crdt_amd.h so
+// that a host in any language reproduces it.  nDev (nil: nMax tuples) chains
+// the call off a merge's device count.  Enqueued: crdt_ctx_sync before reading.
+func SetDigest(lww bool, t *C.crdt_tuples, nMax int, nDev *C.uint64_t, splittersDev *C.uint64_t, m int,
+	hashOutDev, countOutDev *C.uint64_t) error {
+	if t == nil || hashOutDev == nil || countOutDev == nil || nMax < 0 || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	mode := C.int(C.CRDT_SET_ORSET)
+	if lww {
+		mode = C.int(C.CRDT_SET_LWW)
+	}
+	return status(C.crdt_set_digest(gpuCtx, mode, t, C.size_t(nMax), nDev, splittersDev, C.size_t(m), hashOutDev, countOutDev))
+}
+
+// SetDigestDiff: flagsOutDev[b] = 1 iff the digests a and b differ in bucket b
+// (hash or count; a poisoned digest, count ~0, flags every bucket), for
+// nBuckets buckets; their number to nDiffDev.  Enqueued.
+func SetDigestDiff(hashADev, countADev, hashBDev, countBDev *C.uint64_t, nBuckets int, flagsOutDev *C.uint8_t,
+	nDiffDev *C.uint64_t) error {
+	if nBuckets < 0 || nDiffDev == nil {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_set_digest_diff(gpuCtx, hashADev, countADev, hashBDev, countBDev, C.size_t(nBuckets), flagsOutDev,
+		nDiffDev))
+}
+
+// SetSelect: the tuples of merge(t, {}) in the buckets with flagsDev[b] != 0
+// (m + 1 flags over SetDigest's buckets), ascending, into out (capacity nMax),
+// their number to countDev: what a replica ships for the differing ranges.
+// srcOutDev (nil: not wanted) as in SetCompact, for GatherSrc with bColDev
+// nil.  out nil (srcOutDev nil too): the count alone.  Enqueued.
+func SetSelect(lww bool, t *C.crdt_tuples, nMax int, nDev *C.uint64_t, splittersDev *C.uint64_t, m int,
+	flagsDev *C.uint8_t, out *C.crdt_tuples, srcOutDev *C.int64_t, countDev *C.uint64_t) error {
+	if t == nil || flagsDev == nil || countDev == nil || nMax < 0 || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	mode := C.int(C.CRDT_SET_ORSET)
+	if lww {
+		mode = C.int(C.CRDT_SET_LWW)
+	}
+	return status(C.crdt_set_select(gpuCtx, mode, t, C.size_t(nMax), nDev, splittersDev, C.size_t(m), flagsDev, out, srcOutDev,
+		countDev))
+}
+
 // LWWMergeSrc: crdt_lww_merge of two sorted set states in HBM that also names,
 // for every output tuple, the input tuple it is -- srcOutDev[i] >= 0: a's tuple
 // of that index; < 0: b's tuple j as -(j+1) -- the first element in merged

@@ -399,6 +399,73 @@ int crdt_set_delta(crdt_ctx *ctx, int mode, const crdt_tuples *src, size_t ns_ma
 int crdt_set_compact(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
                      const uint64_t *cut_dev, size_t n_cut, const crdt_tuples *out, int64_t *src_out_dev,
                      uint64_t *count_dev);
+/* ---- range digests: find the key ranges in which two set states differ
+ * without shipping either (the reference's gossip pull ships the entire Diff
+ * every round, main.go:153-170 and :245-256; crdt_set_delta needs both states
+ * in one memory).  Both replicas reduce their state to one small fingerprint
+ * per key range, exchange the fingerprints (16 bytes a range), ship only the
+ * ranges whose fingerprints differ, and may recurse with finer splitters
+ * inside those.
+ * Canonical form: canon(t, mode) is the tuples of merge(t, {}), t sorted
+ * ascending by (key, ts, rep), copies of one tag in any order:
+ *   OR-Set : each distinct tag once, tomb = the OR over its copies.
+ *   LWW    : per distinct key the maximal (ts, rep) tag, with the tomb of that
+ *            tag's FIRST copy (crdt_lww_merge's winner).
+ * Buckets: splitters_dev[0 .. m) are ascending uint64 (equal neighbours are
+ * allowed and give empty buckets); they define m + 1 buckets, bucket(key) =
+ * #{ j : splitters[j] <= key } under unsigned compare.  m == 0 (splitters_dev
+ * may then be NULL): one bucket, the whole state.  Unsorted splitters are the
+ * caller's error: the digests are then unspecified, but every access stays in
+ * range.
+ * Tuple hash: with sm(x) the SplitMix64 output function,
+ *   x += 0x9E3779B97F4A7C15;
+ *   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *   x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
+ *   sm = x ^ (x >> 31)                                 (all mod 2^64),
+ *   h(key, ts, rep, tomb) = sm( sm( sm(key) ^ ts ) ^ ((uint64)rep << 1 | tomb) ).
+ * Digest: for every bucket b, hash_out_dev[b] = the sum mod 2^64 of h over
+ * canon(t)'s tuples in b and count_out_dev[b] = their number.  Wrapping adds
+ * are associative and commutative, so the result is bit-exact however the adds
+ * are ordered.  Hence digest(t) == digest(merge(t, {})) == digest(t with any
+ * tuples duplicated); two states agree in a bucket with probability about 1 -
+ * 2^-64 iff their canonical tuples there are equal.  It is a checksum: it
+ * offers no protection against an adversary.
+ * crdt_set_digest writes all m + 1 entries of both outputs (it zeroes them
+ * itself); n_max == 0: all zero.  n_dev follows crdt_set_compact's: NULL ->
+ * n_max tuples; *n_dev <= n_max -> the first *n_dev; *n_dev > n_max -> no tuple
+ * is touched, every entry of both outputs = ~0 and CRDT_DEV_RANGE is raised.
+ * Common to the three calls: stream-ordered, no host synchronisation
+ * (capturable after crdt_ctx_reserve); no kernel reads a tuple at or past
+ * min(*n_dev, n_max), a splitter at or past m or a flag at or past m + 1; key /
+ * ts / rep naturally aligned but otherwise arbitrary (offset views).
+ * CRDT_E_INVAL: NULL ctx / t / an output, bad mode, NULL fields of t or out
+ * with n_max > 0, splitters_dev NULL with m > 0, misalignment (key / ts / rep;
+ * every uint64 / int64 array to 8 bytes), an output overlapping an input or
+ * another output; CRDT_E_RANGE: n_max >= 2^62, m >= 2^24 (n_buckets > 2^24),
+ * or more tiles than a launch holds. */
+int crdt_set_digest(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
+                    const uint64_t *splitters_dev, size_t m, uint64_t *hash_out_dev, uint64_t *count_out_dev);
+/* flags_out_dev[b] = 1 iff the two digests differ in bucket b -- the hashes or
+ * the counts differ, or either count is ~0 (a poisoned digest flags every
+ * bucket, even against another poisoned one) -- else 0, for b < n_buckets;
+ * *n_diff_dev (device uint64) = the number of flagged buckets.  n_buckets ==
+ * 0 stores *n_diff_dev = 0 alone. */
+int crdt_set_digest_diff(crdt_ctx *ctx, const uint64_t *hash_a_dev, const uint64_t *count_a_dev,
+                         const uint64_t *hash_b_dev, const uint64_t *count_b_dev, size_t n_buckets,
+                         uint8_t *flags_out_dev, uint64_t *n_diff_dev);
+/* canon(t) restricted to the buckets with flags_dev[b] != 0 (m + 1 flags, e.g.
+ * crdt_set_digest_diff's), in ascending tuple order into out, their number to
+ * *count_dev: what a replica ships for the differing ranges.  All flags set
+ * equals merge(t, {}) bit for bit; no flag set gives count 0.  src_out_dev
+ * (may be NULL) has crdt_set_compact's meaning and encoding (the index in t of
+ * the first copy of the output's tag), so crdt_src_gather moves value columns
+ * with no read-back.  out may be NULL: the count alone; src_out_dev must then
+ * be NULL.  out holds >= n_max tuples, src_out_dev >= n_max int64.  *n_dev >
+ * n_max: nothing is written to out or src_out_dev, *count_dev = ~0 and
+ * CRDT_DEV_RANGE is raised.  n_max == 0 launches nothing but the count store. */
+int crdt_set_select(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
+                    const uint64_t *splitters_dev, size_t m, const uint8_t *flags_dev,
+                    const crdt_tuples *out, int64_t *src_out_dev, uint64_t *count_dev);
 /* Sortedness check (host-facing validation): *bad_dev = number of adjacent
  * pairs with t[i] > t[i+1]. */
 int crdt_tuples_count_unsorted(crdt_ctx *ctx, const crdt_tuples *t, size_t n,
