@@ -541,6 +541,89 @@ class Engine:
         out, src, count = self.set_compact(t, lww, cut, with_src=True)
         return out, self.gather_src(src, val, val[:0], n_dev=count), count
 
+    # -- the tombstone-free OR-Set: causal merge under version vectors (crdt_orset_merge_causal)
+    def causal_merge(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet, ctx_b: torch.Tensor | None,
+                     n_a_dev: torch.Tensor | None = None, n_b_dev: torch.Tensor | None = None,
+                     out: TupleSet | None = None, src: torch.Tensor | None = None,
+                     ctx_out: torch.Tensor | None = None, count: torch.Tensor | None = None,
+                     with_src: bool = False, trim: bool = False):
+        """Merge of two causal OR-Set states (tuples, context): a tag (key,
+        ts, rep) survives iff it is present in both, or present in one side
+        and not covered by the other side's context.  Present: the side holds
+        a copy and none of its copies is tombstoned; covered by ``ctx``: rep <
+        len(ctx) and ts <= ctx[rep], unsigned (``ctx_a`` / ``ctx_b``: int64
+        storage of uint64 on the device; None: the empty context, which
+        covers nothing).  The caller vouches that each state's context covers
+        its own present tags and is contiguous.  Returns (out, ctx_out,
+        count), or (out, src, ctx_out, count) with ``with_src`` (or a ``src``
+        tensor): device-resident, no synchronisation -- out / src of capacity
+        len(a) + len(b), their first ``count`` entries valid, every out.tomb
+        0; src[i] >= 0: out[i] is a[src[i]], src[i] < 0: it is b[-(src[i] +
+        1)] -- the first copy of the tag on a side that holds it present, a
+        before b -- for :meth:`gather_src`; ctx_out the element-wise maximum
+        of the contexts (the shorter one padded with zeros), written even when
+        a length is out of range.  ``n_a_dev`` / ``n_b_dev`` as in
+        :meth:`set_delta`; with ``trim`` the device status is checked and the
+        sliced results returned."""
+        n = len(a) + len(b)
+        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
+        if len(out) < n:
+            raise ValueError("causal_merge: out holds fewer tuples than len(a) + len(b)")
+        if src is None and with_src:
+            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        if src is not None:
+            self._check(src, itemsize=8)
+            if src.dtype != torch.int64 or src.numel() < n:
+                raise ValueError("causal_merge: src must be int64 and hold len(a) + len(b) entries")
+        nc = max(0 if ctx_a is None else ctx_a.numel(), 0 if ctx_b is None else ctx_b.numel())
+        ctx_out = torch.empty(nc, dtype=torch.int64, device=self.device) if ctx_out is None else ctx_out
+        self._check(ctx_out, itemsize=8)
+        if ctx_out.numel() < nc:
+            raise ValueError("causal_merge: ctx_out holds fewer entries than the longer context")
+        count = self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out, count)
+        if trim:
+            self.check_device()
+            k = int(count.item())
+            return (out.slice(k), ctx_out, count) if src is None else (out.slice(k), src[:k], ctx_out, count)
+        return (out, ctx_out, count) if src is None else (out, src, ctx_out, count)
+
+    def causal_merge_count(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet, ctx_b: torch.Tensor | None,
+                           n_a_dev: torch.Tensor | None = None, n_b_dev: torch.Tensor | None = None,
+                           count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(causal_merge(a, b)) alone (int64[1] on the device, no
+        synchronisation): nothing is written but the count."""
+        return self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, None, None, None, count)
+
+    def _causal_merge(self, a: TupleSet, ctx_a, b: TupleSet, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out,
+                      count) -> torch.Tensor:
+        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        self._check(count, itemsize=8)
+        for s in (a, b) + (() if out is None else (out,)):
+            self._check(s.key, s.ts, itemsize=8)
+            self._check(s.rep, itemsize=4)
+            self._check(s.tomb, itemsize=1)
+        for x in (ctx_a, ctx_b, n_a_dev, n_b_dev):
+            if x is not None:
+                self._check(x, itemsize=8)
+        ca, cb = a.c(), b.c()
+        co = None if out is None else out.c()
+        self._call("crdt_orset_merge_causal", C.byref(ca), len(a), _ptr(n_a_dev), _ptr(ctx_a),
+                   0 if ctx_a is None else ctx_a.numel(), C.byref(cb), len(b), _ptr(n_b_dev), _ptr(ctx_b),
+                   0 if ctx_b is None else ctx_b.numel(), None if co is None else C.byref(co), _ptr(src),
+                   _ptr(ctx_out), count.data_ptr())
+        return count
+
+    def causal_map_merge(self, a: TupleSet, a_val: torch.Tensor, ctx_a: torch.Tensor | None, b: TupleSet,
+                         b_val: torch.Tensor, ctx_b: torch.Tensor | None):
+        """:meth:`causal_merge` of states that keep a value beside each tuple
+        (a_val[i] belongs to a's tuple i): returns (out, out_val, ctx_out,
+        count), device-resident -- the merge, then one :meth:`gather_src`
+        chained off its device count, no read-back."""
+        if a_val.shape[0] != len(a) or b_val.shape[0] != len(b):
+            raise ValueError("causal_map_merge: one value per tuple on each side")
+        out, src, ctx_out, count = self.causal_merge(a, ctx_a, b, ctx_b, with_src=True)
+        return out, self.gather_src(src, a_val, b_val, n_dev=count), ctx_out, count
+
     # -- range digests: where two states differ, without shipping either
     #    (crdt_set_digest / crdt_set_digest_diff / crdt_set_select)
     def _check_tuples(self, *sets: TupleSet) -> None:

@@ -255,6 +255,38 @@ func SetCompactCount(lww bool, t *C.crdt_tuples, nMax int, nDev *C.uint64_t, cut
 	return SetCompact(lww, t, nMax, nDev, cutDev, nCut, nil, nil, countDev)
 }
 
+// OrsetMergeCausal: the merge of two tombstone-free OR-Set states, each a pair
+// of sorted tuples and a causal context (ctxDev[r] = the events of replica r
+// the state has seen).  A tag survives iff both sides hold it present (a copy,
+// none tombstoned), or one side does and the other side's context does not
+// cover it (rep < nCtx and ts <= ctxDev[rep]): a side whose context covers a
+// tag it does not hold has seen and removed it.  No tombstone is kept and no
+// population-wide cut is needed, where SetCompact needs StableCut over every
+// replica's clock.  The surviving tags go to out in ascending order, tomb 0
+// (capacity naMax + nbMax), their number to countDev; srcOutDev (nil: not
+// wanted; same capacity) receives per output tuple the first copy of its tag
+// on a side that holds it present, a before b, in OrsetMergeSrc's encoding,
+// for GatherSrc; ctxOutDev (nil: not wanted; max(nCtxA, nCtxB) entries) the
+// element-wise maximum of the contexts.  naDev / nbDev (nil: all nMax tuples of
+// the side) chain the call off device counts with no read-back.  The caller
+// vouches that each context covers its own state's present tags and is
+// contiguous.  Enqueued: crdt_ctx_sync before reading.
+func OrsetMergeCausal(a *C.crdt_tuples, naMax int, naDev, ctxADev *C.uint64_t, nCtxA int, b *C.crdt_tuples, nbMax int,
+	nbDev, ctxBDev *C.uint64_t, nCtxB int, out *C.crdt_tuples, srcOutDev *C.int64_t, ctxOutDev, countDev *C.uint64_t) error {
+	if a == nil || b == nil || countDev == nil || naMax < 0 || nbMax < 0 || nCtxA < 0 || nCtxB < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_orset_merge_causal(gpuCtx, a, C.size_t(naMax), naDev, ctxADev, C.size_t(nCtxA), b, C.size_t(nbMax),
+		nbDev, ctxBDev, C.size_t(nCtxB), out, srcOutDev, ctxOutDev, countDev))
+}
+
+// OrsetMergeCausalCount: the size of that merge alone (nothing stored but the
+// count) -- the live tags the two replicas hold between them.
+func OrsetMergeCausalCount(a *C.crdt_tuples, naMax int, naDev, ctxADev *C.uint64_t, nCtxA int, b *C.crdt_tuples, nbMax int,
+	nbDev, ctxBDev *C.uint64_t, nCtxB int, countDev *C.uint64_t) error {
+	return OrsetMergeCausal(a, naMax, naDev, ctxADev, nCtxA, b, nbMax, nbDev, ctxBDev, nCtxB, nil, nil, nil, countDev)
+}
+
 // SetDigest: one order-independent fingerprint per key range of the sorted set
 // state t -- hashOutDev[b] = the wrapping sum of the tuple hash over the
 // tuples of merge(t, {}) whose key falls into bucket b, countOutDev[b] their

@@ -399,6 +399,80 @@ int crdt_set_delta(crdt_ctx *ctx, int mode, const crdt_tuples *src, size_t ns_ma
 int crdt_set_compact(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
                      const uint64_t *cut_dev, size_t n_cut, const crdt_tuples *out, int64_t *src_out_dev,
                      uint64_t *count_dev);
+/* ---- the tombstone-free OR-Set: a causal merge under version vectors (no
+ * reference counterpart; the optimised OR-Set of Bieniusa et al., Riak's
+ * ORSWOT).  crdt_set_compact drops a tombstone only under a cut over ALL
+ * replicas' clocks; here every state carries its own causal context instead
+ * and a remove leaves nothing behind, so state is proportional to the live
+ * tags and no population-wide cut is ever needed.
+ * A causal state is a pair (tuples, context): tuples sorted ascending by (key,
+ * ts, rep), copies of one tag in any order and any number on either side; the
+ * context ctx_dev[0 .. n_ctx) of uint64, ctx[r] = the events of replica r the
+ * state has seen (n_ctx == 0: ctx_dev may be NULL).
+ * Present: side X holds tag g = (key, ts, rep) as present iff it holds at least
+ * one copy of g and the OR of its copies' tombs is 0 -- crdt_set_elements' live
+ * tag.  A tombstoned tag counts as absent, which is also the way in from the
+ * tombstone form: merge a tombstone-form state with its replica's clock.
+ * Covered: covered(g, v, n) iff g.rep < n and g.ts <= v[g.rep] (unsigned
+ * compare) -- crdt_set_compact's "stable".  A rep at or past n is never
+ * covered; with n == 0 nothing is.
+ * Merge rule: tag g is in merge(a, b) iff
+ *   g is present in a and in b, or
+ *   g is present in a and not covered by b's context, or
+ *   g is present in b and not covered by a's context
+ * (a side whose context covers a tag it does not hold has seen and removed it).
+ * out receives each surviving tag once, in ascending tuple order, with tomb =
+ * 0; *count_dev (device uint64) their number: a sorted state the merges, reads,
+ * deltas and digests accept.
+ * src_out_dev (may be NULL): per output tuple the input tuple it is, in
+ * crdt_orset_merge_src's encoding (>= 0 an index into a; < 0 b's index j as
+ * -(j + 1)), so crdt_src_gather moves value columns with no read-back.  Merged
+ * order is the stable merge of a and b: a's copies of a tag before b's, each
+ * side in its input order.  The copy named is the first copy, in merged order,
+ * ON A SIDE WHERE THE TAG IS PRESENT: a's first copy of the tag when a holds it
+ * present, otherwise b's first copy.  So with a tombstoned copy on a and the
+ * live one on b (a surviving tag then: present in b, not covered by a's
+ * context) b's first copy is named, not the tag's first copy in merged order;
+ * the copy named may itself carry tomb = 0 only (a present side has no other).
+ * ctx_out_dev (may be NULL): max(n_ctx_a, n_ctx_b) uint64, ctx_out[c] =
+ * max(c < n_ctx_a ? ctx_a[c] : 0, c < n_ctx_b ? ctx_b[c] : 0).  It depends on
+ * the contexts only and is written whatever the lengths are (a poisoned length
+ * included).  It must not overlap any input.
+ * out may be NULL: the count alone (no bitmaps, no offsets); src_out_dev must
+ * then be NULL too and nothing is stored but *count_dev and ctx_out_dev.
+ * THE CALLER'S OBLIGATION (not enforced): every present tag of a state is
+ * covered by that state's own context, and contexts are contiguous -- v[r] = n
+ * means the state has seen events 1 .. n of r (ts counts rep's events, as in
+ * crdt_set_compact's contract).  Under these the merge is commutative (equal
+ * tuples and equal ctx_out for either operand order), associative and
+ * idempotent (merge(A, A) = A's present tags), and (out, ctx_out) is again
+ * such a state.  Local adds and removes are the host's: an add appends (key,
+ * ++ctx[r], r), a remove deletes the key's tuples and leaves the context.
+ * na_dev / nb_dev follow crdt_set_delta's ns_dev, each on its own: NULL -> all
+ * n_max tuples of the side; <= n_max -> the first so many; > n_max on either
+ * side -> no tuple of either side is touched, nothing is written to out or
+ * src_out_dev, *count_dev = ~0 and CRDT_DEV_RANGE is raised.  No kernel reads a
+ * tuple at or past min(*n_dev, n_max) of its side or before 0 (the write pass
+ * checks every position of its bitmaps against those lengths before it loads),
+ * nor a context at or past its n_ctx.  Stream-ordered, no host synchronisation;
+ * workspace from the context only (capturable after crdt_ctx_reserve).  key /
+ * ts / rep naturally aligned but otherwise at arbitrary offsets.  out holds >=
+ * na_max + nb_max tuples, src_out_dev as many int64; neither may overlap an
+ * input, ctx_out_dev or the other.
+ * CRDT_E_INVAL: NULL ctx / a / b / count_dev, NULL fields of a side with n_max
+ * > 0 or of out with na_max + nb_max > 0, key / ts / rep of any operand not
+ * naturally aligned, a context NULL with its n_ctx > 0, a context, na_dev,
+ * nb_dev, src_out_dev, ctx_out_dev or count_dev not 8-byte aligned, src_out_dev
+ * without out, an overlap as above; CRDT_E_RANGE: na_max or nb_max >= 2^62,
+ * n_ctx_a or n_ctx_b >= 2^32, or more tiles than a launch holds.  na_max +
+ * nb_max == 0 launches nothing but the count store and the ctx_out write. */
+int crdt_orset_merge_causal(crdt_ctx *ctx,
+                            const crdt_tuples *a, size_t na_max, const uint64_t *na_dev,
+                            const uint64_t *ctx_a_dev, size_t n_ctx_a,
+                            const crdt_tuples *b, size_t nb_max, const uint64_t *nb_dev,
+                            const uint64_t *ctx_b_dev, size_t n_ctx_b,
+                            const crdt_tuples *out, int64_t *src_out_dev, uint64_t *ctx_out_dev,
+                            uint64_t *count_dev);
 /* ---- range digests: find the key ranges in which two set states differ
  * without shipping either (the reference's gossip pull ships the entire Diff
  * every round, main.go:153-170 and :245-256; crdt_set_delta needs both states
