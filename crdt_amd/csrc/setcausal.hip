@@ -23,8 +23,7 @@
 // decision taken at the LAST merged item of a tag run (an a item exactly when
 // b holds no copy of the tag):
 //   ctx   : ctx_out alone, whatever the lengths are;
-//   split : merge-path splits of every 2048-item tile (the 16-ary search of
-//           k_delta_split, the lengths read on the device);
+//   split : k_mp_split (settile.hpp) by the full tag;
 //   count : per tile both runs staged in LDS (plain loads, clamped to each
 //           side's length) and merged, 512 threads x 4 items.  A thread
 //           carries the open tag run's state (a copy seen, a tomb-OR, b copy
@@ -37,16 +36,15 @@
 //           the scan re-decides, records both covered bits.  Output: bitmaps
 //           in merged order (`isb`: a b item, `emit`, `srca`: the emitted tag
 //           is present in a), the tile's count and record;
-//   scan  : one workgroup, rounds of 16384 tiles: the carries into all tiles
-//           as a scan of the records (linear however many tiles a tag spans),
-//           each tile's first run end re-decided under its carry, the counts
-//           to offsets, the total to *count;
-//   write : (out != NULL) one output per lane, by rank: the rank's emit bit is
-//           selected from the tile's bitmap, its side and index there are
-//           prefix popcounts of `isb`; key / ts / rep of the run end stored at
+//   scan  : k_tile_scan<CausalCarry> (settile.hpp): the records scan as they
+//           are, each tile's first run end is re-decided with the carry's
+//           bits ORed into its run's own, under the recorded covered bits;
+//   write : (out != NULL) one output per lane, by rank (rank_words /
+//           rank_select, settile.hpp): its side and index there follow from
+//           the count of b items before it; key / ts / rep of the run end stored at
 //           the rank with tomb = 0, and, when asked, the source index: the
 //           walk back over the present side's equal-tag copies to the first
-//           one goes through global memory, as k_cmp_write's does (from a's
+//           one goes through global memory, as k_tile_write's does (from a's
 //           last copy, the a item merged just before b's copies, when the run
 //           ends on b).
 //
@@ -54,17 +52,16 @@
 // tuple, stores a count of ~0 and raises CRDT_DEV_RANGE; no kernel reads an
 // index at or past min(*n_dev, n_max) of its side, or before 0, nor a context
 // at or past its n_ctx.
-#include "common.hpp"
+#include "settile.hpp"
 
 namespace crdt {
 
-constexpr int UT = 2048;                   // merge items per tile
+constexpr int UT = kTile;                  // merge items per tile
 constexpr int UCB = 512;                   // count pass threads
 constexpr int UNI = UT / UCB;              // merge items per count thread
-constexpr int UNW = UT / 64;               // words per tile and bitmap
+constexpr int UNW = kTileNW;               // words per tile and bitmap
 constexpr int UWB = 256;                   // write pass threads (one output each per round)
 constexpr int UCAP = UT + 4;               // staged slots: each side's run, the element before and the one after it
-constexpr uint32_t kCausalScanMax = 16384; // tiles per scan round (16 per thread)
 
 // ---- the open tag run's state and a segment's record
 constexpr uint32_t kUHasA = 1, kUTorA = 2, kUHasB = 4, kUTorB = 8;   // a / b: copy seen, tomb-OR
@@ -94,23 +91,24 @@ __device__ __forceinline__ uint32_t cz_decide(uint32_t s, uint64_t ts, uint32_t 
     return (keep ? 1u : 0u) | (keep && pa ? 2u : 0u);
 }
 
-// both lengths, each n_max or its device count; false when either is out of range
-__device__ __forceinline__ bool cz_len(uint64_t na_max, const uint64_t *__restrict__ na_dev, uint64_t nb_max,
-                                       const uint64_t *__restrict__ nb_dev, uint64_t *na, uint64_t *nb) {
-    *na = na_dev ? *na_dev : na_max;
-    *nb = nb_dev ? *nb_dev : nb_max;
-    return *na <= na_max && *nb <= nb_max;
-}
-__device__ __forceinline__ uint64_t cz_tiles(uint64_t na, uint64_t nb) { return (na + nb + UT - 1) / UT; }
-
-// A[i] <= B[j] in merge order (ts / rep read only on a key tie)
-__device__ __forceinline__ bool cz_le(const crdt_tuples &A, uint64_t i, const crdt_tuples &B, uint64_t j) {
-    const uint64_t ka = A.key[i], kb = B.key[j];
-    if (ka != kb) return ka < kb;
-    const uint64_t ta = A.ts[i], tb = B.ts[j];
-    if (ta != tb) return ta < tb;
-    return A.rep[i] <= B.rep[j];
-}
+// the scan's view of a record: the state scans as it is; the first run end is
+// re-decided with the carry's bits ORed into its run's own, under the recorded covered bits
+struct CausalCarry : PlainTiles {
+    static constexpr bool kHas = true;
+    static constexpr uint32_t kId = 0, kStride = 3 * UNW, kEmit = UNW, kAux = 2 * UNW;   // (`isb`, `emit`, `srca`)
+    static __device__ __forceinline__ uint32_t part(uint32_t r) { return r & 0x1fu; }
+    static __device__ __forceinline__ uint32_t then(uint32_t a, uint32_t b) { return cz_then(a, b); }
+    static __device__ __forceinline__ uint32_t seed(uint32_t s) { return s; }
+    static __device__ __forceinline__ uint32_t enter(uint32_t p, uint32_t) { return p; }
+    static __device__ __forceinline__ uint32_t step(uint32_t s, uint32_t r) { return cz_then(s, r & 0x1fu); }
+    static __device__ __forceinline__ uint32_t redecide(uint32_t r, uint32_t s) {
+        if (!((r & kUEnd) && (s & kURun))) return 0;     // (an empty carry changes nothing)
+        const uint32_t own = (r >> 5) & kURun, all = own | (s & kURun);
+        const bool cva = (r >> 9) & 1, cvb = (r >> 10) & 1;
+        const uint32_t d0 = cz_keep(own, cva, cvb), d1 = cz_keep(all, cva, cvb);
+        return redo(r >> 16, ((d0 ^ d1) & 1) != 0, ((d0 ^ d1) & 2) != 0, (d1 & 1) != 0);
+    }
+};
 
 // ---------------------------------------------------------------- ctx_out
 __global__ __launch_bounds__(256) void k_causal_ctx(const uint64_t *__restrict__ ca, uint32_t nca,
@@ -121,47 +119,6 @@ __global__ __launch_bounds__(256) void k_causal_ctx(const uint64_t *__restrict__
     if (c >= n) return;
     const uint64_t x = c < nca ? ca[c] : 0ull, y = c < ncb ? cb[c] : 0ull;
     out[c] = x > y ? x : y;
-}
-
-// ---------------------------------------------------------------- split
-// split[t] = a elements among the first min(t UT, n) merged items, t = 0 ..
-// tiles: one 16-lane group per diagonal, four per wave.
-__global__ __launch_bounds__(256) void k_causal_split(crdt_tuples A, uint64_t na_max, const uint64_t *__restrict__ na_dev,
-                                                      crdt_tuples B, uint64_t nb_max, const uint64_t *__restrict__ nb_dev,
-                                                      uint64_t *__restrict__ split) {
-    uint64_t na, nb;
-    if (!cz_len(na_max, na_dev, nb_max, nb_dev, &na, &nb)) return;
-    const uint64_t ntiles = cz_tiles(na, nb);
-    if (ntiles == 0) return;
-    const int lane = threadIdx.x & 63, grp = lane >> 4, gl = lane & 15;
-    const uint64_t t = ((((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6) << 2) + (uint64_t)grp;
-    const uint64_t n = na + nb;
-    const uint64_t d = t < ntiles ? t * UT : n;
-    uint64_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
-    bool done = t > ntiles || hi <= lo;
-    // P(i) = A[i] <= B[d-1-i]: true below the split, false from it
-    while (__ballot(!done)) {
-        const uint64_t span = hi - lo;
-        const bool small = span <= 16;
-        const uint64_t c = small ? lo + (uint64_t)gl : lo + ((uint64_t)gl * span) / 16;
-        const bool valid = !done && (small ? (uint64_t)gl < span : true);
-        const bool p = valid && cz_le(A, c, B, d - 1 - c);
-        const unsigned m = (unsigned)((__ballot(p) >> (grp * 16)) & 0xFFFF);
-        const unsigned cnt = (unsigned)__popc(m);
-        if (!done) {
-            if (small) {
-                lo += cnt;
-                done = true;
-            } else {
-                const uint64_t nlo = cnt > 0 ? lo + (((uint64_t)(cnt - 1)) * span) / 16 + 1 : lo;
-                const uint64_t nhi = cnt < 16 ? lo + ((uint64_t)cnt * span) / 16 : hi;
-                lo = nlo;
-                hi = nhi;
-                done = hi <= lo;
-            }
-        }
-    }
-    if (gl == 0 && t <= ntiles) split[t] = lo;
 }
 
 // ---------------------------------------------------------------- count
@@ -179,9 +136,9 @@ __global__ __launch_bounds__(UCB) void k_causal_count(crdt_tuples A, uint64_t na
     __shared__ uint8_t sm[UCAP];
     __shared__ uint32_t s_w[UCB / 64], s_c[UCB / 64], s_first;
     uint64_t na, nb;
-    if (!cz_len(na_max, na_dev, nb_max, nb_dev, &na, &nb)) return;
+    if (!tile_len(na_max, na_dev, nb_max, nb_dev, &na, &nb)) return;
     const uint64_t t = blockIdx.x;
-    if (t >= cz_tiles(na, nb)) return;                   // (uniform)
+    if (t >= PlainTiles::tiles(na, nb)) return;                   // (uniform)
     const uint64_t n = na + nb, d0 = t * UT, d1 = d0 + UT < n ? d0 + UT : n;
     const uint64_t i0 = split[t], i1 = split[t + 1], j0 = d0 - i0, j1 = d1 - i1;
     const uint32_t ta = (uint32_t)(i1 - i0), tb = (uint32_t)(j1 - j0), tn = ta + tb;
@@ -338,111 +295,6 @@ __global__ __launch_bounds__(UCB) void k_causal_count(crdt_tuples A, uint64_t na
     }
 }
 
-// ---------------------------------------------------------------- carry + scan
-// One workgroup, rounds of up to kCausalScanMax tiles (a contiguous run of 16
-// tiles per thread): the carry into every tile as a scan of the records, the
-// first run end of each tile re-decided under its carry (emit and srca bits,
-// when given, and the count); then the counts to offsets (ic, when given;
-// ic[tiles] = the total) and the total to *count.
-__global__ __launch_bounds__(1024) void k_causal_scan(uint64_t na_max, const uint64_t *__restrict__ na_dev,
-                                                      uint64_t nb_max, const uint64_t *__restrict__ nb_dev,
-                                                      const uint32_t *__restrict__ tcnt, const uint32_t *__restrict__ rec,
-                                                      uint64_t *__restrict__ bits, uint64_t *__restrict__ ic,
-                                                      uint64_t *__restrict__ count, uint32_t *__restrict__ err) {
-    constexpr int K = kCausalScanMax / 1024;
-    __shared__ uint32_t s_f[16];
-    __shared__ uint64_t s_c[16];
-    uint64_t na, nb;
-    if (!cz_len(na_max, na_dev, nb_max, nb_dev, &na, &nb)) {
-        if (threadIdx.x == 0) {
-            *count = ~0ull;
-            atomicOr(err, CRDT_DEV_RANGE);
-        }
-        return;
-    }
-    const uint64_t nt = cz_tiles(na, nb);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t state = 0;                                  // the carry into the round's first tile
-    uint64_t base = 0;
-    for (uint64_t c0 = 0; c0 < nt; c0 += kCausalScanMax) {
-        const uint64_t b = c0 + (uint64_t)threadIdx.x * K;
-        uint32_t v[K], rr[K], f = 0;
-#pragma unroll
-        for (int q = 0; q < K; ++q) v[q] = b + q < nt ? tcnt[b + q] : 0u;
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-            rr[q] = b + q < nt ? rec[b + q] : 0u;
-            f = cz_then(f, rr[q] & 0x1fu);
-        }
-        {
-            uint32_t x = f;                              // inclusive scan over the wave's threads
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = __shfl_up(x, o, 64);
-                if (lane >= o) x = cz_then(y, x);
-            }
-            if (lane == 63) s_f[w] = x;
-            uint32_t ex = __shfl_up(x, 1, 64);
-            if (lane == 0) ex = 0;
-            __syncthreads();
-            uint32_t pre = state, tot = state;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if (q < w) pre = cz_then(pre, s_f[q]);
-                tot = cz_then(tot, s_f[q]);
-            }
-            uint32_t s = cz_then(pre, ex);
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                const uint32_t r = rr[q];
-                if ((r & kUEnd) && (s & kURun)) {        // (a tile past nt holds no end; an empty carry changes nothing)
-                    const uint32_t own = (r >> 5) & kURun, all = own | (s & kURun);
-                    const bool cva = (r >> 9) & 1, cvb = (r >> 10) & 1;
-                    const uint32_t d0 = cz_keep(own, cva, cvb), d1 = cz_keep(all, cva, cvb);
-                    const uint32_t p = r >> 16;
-                    if ((d0 ^ d1) & 1) {
-                        if (bits) bits[(b + q) * (3 * UNW) + UNW + (p >> 6)] ^= 1ull << (p & 63);
-                        v[q] += (d1 & 1) ? 1u : 0xffffffffu;
-                    }
-                    if (bits && ((d0 ^ d1) & 2)) bits[(b + q) * (3 * UNW) + 2 * UNW + (p >> 6)] ^= 1ull << (p & 63);
-                }
-                s = cz_then(s, r & 0x1fu);
-            }
-            state = tot;
-        }
-        uint64_t sum = 0;
-#pragma unroll
-        for (int q = 0; q < K; ++q) sum += v[q];
-        uint64_t x = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_c[w] = x;
-        __syncthreads();
-        uint64_t run = base + x - sum, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            run += q < w ? s_c[q] : 0;
-            tot += s_c[q];
-        }
-        if (ic) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                if (b + q < nt) ic[b + q] = run;
-                run += v[q];
-            }
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (ic) ic[nt] = base;
-        *count = base;
-    }
-}
-
 // ---------------------------------------------------------------- write pass
 template <bool SRC>
 __global__ __launch_bounds__(UWB) void k_causal_write(crdt_tuples A, uint64_t na_max, const uint64_t *__restrict__ na_dev,
@@ -452,27 +304,14 @@ __global__ __launch_bounds__(UWB) void k_causal_write(crdt_tuples A, uint64_t na
                                                       crdt_tuples out, int64_t *__restrict__ src,
                                                       uint32_t *__restrict__ err) {
     uint64_t na, nb;
-    if (!cz_len(na_max, na_dev, nb_max, nb_dev, &na, &nb)) return;
+    if (!tile_len(na_max, na_dev, nb_max, nb_dev, &na, &nb)) return;
     const uint64_t t = blockIdx.x;
-    if (t >= cz_tiles(na, nb)) return;
+    if (t >= PlainTiles::tiles(na, nb)) return;
     const int lane = threadIdx.x & 63;
     const uint64_t *b = bits + t * (3 * UNW);
-    // every wave holds the tile's words, lane w word w, and their exclusive prefix counts
-    const uint64_t wb = lane < UNW ? b[lane] : 0ull, we = lane < UNW ? b[UNW + lane] : 0ull;
+    const RankWords k = rank_words(b, lane);              // `isb`, `emit` and their prefix counts
     const uint64_t wa = SRC && lane < UNW ? b[2 * UNW + lane] : 0ull;
-    const uint32_t pb = (uint32_t)__popcll(wb), pe = (uint32_t)__popcll(we);
-    uint32_t xb = pb, xe = pe;
-#pragma unroll
-    for (int o = 1; o < UNW; o <<= 1) {
-        const uint32_t yb = __shfl_up(xb, o, 64), ye = __shfl_up(xe, o, 64);
-        if (lane >= o) {
-            xb += yb;
-            xe += ye;
-        }
-    }
-    const uint32_t ne = (uint32_t)__builtin_amdgcn_readlane((int)xe, UNW - 1);   // the tile's outputs
-    xb -= pb;
-    xe -= pe;
+    const uint32_t ne = k.ne;
     const uint64_t i0 = split[t], j0 = t * UT - i0, base = ic[t], cap = na_max + nb_max;
     bool bad = false;
     // one output per thread and round, by rank: every lane of a wave loads and
@@ -480,33 +319,18 @@ __global__ __launch_bounds__(UWB) void k_causal_write(crdt_tuples A, uint64_t na
     for (uint32_t r0 = 0; r0 < ne; r0 += UWB) {          // (uniform: the shuffles below read every word's lane)
         const bool valid = r0 + threadIdx.x < ne;
         const uint32_t r = valid ? r0 + threadIdx.x : ne - 1;
-        int w = 0;                                       // the last word with xe <= r: the one holding output r
-#pragma unroll
-        for (int o = UNW / 2; o > 0; o >>= 1)
-            if (__shfl(xe, w + o, 64) <= r) w += o;
-        const uint64_t qb = (uint64_t)__shfl((unsigned long long)wb, w, 64);
-        const uint64_t qe = (uint64_t)__shfl((unsigned long long)we, w, 64);
-        const uint64_t qa = SRC ? (uint64_t)__shfl((unsigned long long)wa, w, 64) : 0ull;
-        const uint32_t bw = __shfl(xb, w, 64);           // b items before the word
-        uint32_t k = r - __shfl(xe, w, 64), pos = 0;     // its set bit of qe, counted from bit 0
-        uint64_t m = qe;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t c = (uint32_t)__popcll(m & ((1ull << o) - 1));
-            if (k >= c) {
-                k -= c;
-                m >>= o;
-                pos += o;
-            }
-        }
+        const RankHit h = rank_select(k, r);
+        const uint64_t qb = h.qb, qe = h.qe;
+        const uint64_t qa = SRC ? (uint64_t)__shfl((unsigned long long)wa, h.w, 64) : 0ull;
+        const uint32_t pos = h.pos;
         if (!valid) continue;
         // (the bitmaps of this call's count pass never fail the checks below)
-        if (!(pos < 64 && ((qe >> pos) & 1))) {
+        if (!((qe >> pos) & 1)) {
             bad = true;
             continue;
         }
-        const uint32_t bb = bw + (uint32_t)__popcll(qb & ((1ull << pos) - 1));   // b items merged before this one
-        const uint32_t ab = (uint32_t)w * 64 + pos - bb;                         // a items
+        const uint32_t bb = h.nb;                            // b items merged before this one
+        const uint32_t ab = (uint32_t)h.w * 64 + pos - bb;   // a items
         const bool is_b = (qb >> pos) & 1;
         const uint64_t i = is_b ? j0 + bb : i0 + ab;     // the run end's index on its side
         const uint64_t at = base + r;
@@ -553,13 +377,6 @@ struct CausalSpan {
     const void *p;
     size_t bytes;
 };
-static bool causal_overlap(const CausalSpan &a, const CausalSpan &b) {
-    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
-    return a.p && b.p && a.bytes && b.bytes && x < y + b.bytes && y < x + a.bytes;
-}
-static bool causal_misaligned(const crdt_tuples *t) {
-    return ((((uintptr_t)t->key | (uintptr_t)t->ts) & 7) | ((uintptr_t)t->rep & 3)) != 0;
-}
 static int causal_fields(const crdt_tuples *t, size_t n, CausalSpan *s) {
     s[0] = {t->key, n * 8};
     s[1] = {t->ts, n * 8};
@@ -584,14 +401,14 @@ extern "C" int crdt_orset_merge_causal(crdt_ctx *ctx, const crdt_tuples *a, size
     if (n_ctx_a >= (1ULL << 32) || n_ctx_b >= (1ULL << 32)) return CRDT_E_RANGE;
     if ((n_ctx_a && !ctx_a_dev) || (n_ctx_b && !ctx_b_dev)) return CRDT_E_INVAL;
     if (!out && src_out_dev) return CRDT_E_INVAL;
-    if (na_max && (!a->key || !a->ts || !a->rep || !a->tomb)) return CRDT_E_INVAL;
-    if (nb_max && (!b->key || !b->ts || !b->rep || !b->tomb)) return CRDT_E_INVAL;
-    if (causal_misaligned(a) || causal_misaligned(b) || (out && causal_misaligned(out))) return CRDT_E_INVAL;
+    if (na_max && tuples_null(a)) return CRDT_E_INVAL;
+    if (nb_max && tuples_null(b)) return CRDT_E_INVAL;
+    if (tuples_misaligned(a) || tuples_misaligned(b) || (out && tuples_misaligned(out))) return CRDT_E_INVAL;
     if ((((uintptr_t)ctx_a_dev | (uintptr_t)ctx_b_dev | (uintptr_t)ctx_out_dev | (uintptr_t)src_out_dev |
           (uintptr_t)na_dev | (uintptr_t)nb_dev | (uintptr_t)count) & 7) != 0)
         return CRDT_E_INVAL;
     const size_t cap = na_max + nb_max, n_ctx = n_ctx_a > n_ctx_b ? n_ctx_a : n_ctx_b;
-    if (out && cap && (!out->key || !out->ts || !out->rep || !out->tomb)) return CRDT_E_INVAL;
+    if (out && cap && tuples_null(out)) return CRDT_E_INVAL;
     const size_t ntiles = (cap + UT - 1) / UT;
     if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;
     {
@@ -607,45 +424,38 @@ extern "C" int crdt_orset_merge_causal(crdt_ctx *ctx, const crdt_tuples *a, size
         o[no++] = {ctx_out_dev, n_ctx * 8};
         for (int x = 0; x < no; ++x) {
             for (int y = 0; y < ni; ++y)
-                if (causal_overlap(o[x], in[y])) return CRDT_E_INVAL;
+                if (spans_overlap(o[x].p, o[x].bytes, in[y].p, in[y].bytes)) return CRDT_E_INVAL;
             for (int y = x + 1; y < no; ++y)
-                if (causal_overlap(o[x], o[y])) return CRDT_E_INVAL;
+                if (spans_overlap(o[x].p, o[x].bytes, o[y].p, o[y].bytes)) return CRDT_E_INVAL;
         }
     }
-    const size_t need = Carve::round((ntiles + 2) * 8) + 2 * Carve::round((ntiles + 1) * 4) +
-                        Carve::round((ntiles + 1) * 8) + Carve::round((ntiles * 3 * UNW + 1) * 8) + 1280;
-    rc = ws_reserve(ctx, need);
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, true, true, 3 * UNW);
     if (rc) return rc;
-    Carve w(ctx->ws);
-    uint64_t *split = w.take<uint64_t>(ntiles + 2);
-    uint32_t *tcnt = w.take<uint32_t>(ntiles + 1);
-    uint32_t *rec = w.take<uint32_t>(ntiles + 1);
-    uint64_t *ic = w.take<uint64_t>(ntiles + 1);
-    uint64_t *bits = w.take<uint64_t>(ntiles * 3 * UNW + 1);
     const bool wr = out != nullptr;
     const uint32_t nca = (uint32_t)n_ctx_a, ncb = (uint32_t)n_ctx_b;
     const hipStream_t s = ctx->stream;
     if (ctx_out_dev && n_ctx)
         k_causal_ctx<<<(unsigned)((n_ctx + 255) / 256), 256, 0, s>>>(ctx_a_dev, nca, ctx_b_dev, ncb, ctx_out_dev);
     if (ntiles) {
-        const unsigned g = (unsigned)ntiles, gs = (unsigned)((ntiles + 1 + 15) / 16);   // 16 diagonals per split workgroup
-        k_causal_split<<<gs, 256, 0, s>>>(*a, na_max, na_dev, *b, nb_max, nb_dev, split);
+        const unsigned g = (unsigned)ntiles;
+        k_mp_split<UT, TupleLe<false>, PlainTiles><<<mp_split_grid(ntiles), 256, 0, s>>>(*a, na_max, na_dev, *b, nb_max,
+                                                                                        nb_dev, w.split);
         if (wr)
             k_causal_count<true><<<g, UCB, 0, s>>>(*a, na_max, na_dev, ctx_a_dev, nca, *b, nb_max, nb_dev, ctx_b_dev, ncb,
-                                                   split, tcnt, rec, bits);
+                                                   w.split, w.tcnt, w.rec, w.bits);
         else
             k_causal_count<false><<<g, UCB, 0, s>>>(*a, na_max, na_dev, ctx_a_dev, nca, *b, nb_max, nb_dev, ctx_b_dev,
-                                                    ncb, split, tcnt, rec, bits);
+                                                    ncb, w.split, w.tcnt, w.rec, w.bits);
     }
-    k_causal_scan<<<1, 1024, 0, s>>>(na_max, na_dev, nb_max, nb_dev, tcnt, rec, wr ? bits : nullptr, wr ? ic : nullptr,
-                                     count, ctx->dev_status);
+    w.scan<CausalCarry>(ctx, na_max, na_dev, nb_max, nb_dev, wr, count);
     if (ntiles && wr) {
         if (src_out_dev)
-            k_causal_write<true><<<(unsigned)ntiles, UWB, 0, s>>>(*a, na_max, na_dev, *b, nb_max, nb_dev, split, bits, ic,
-                                                                  *out, src_out_dev, ctx->dev_status);
+            k_causal_write<true><<<(unsigned)ntiles, UWB, 0, s>>>(*a, na_max, na_dev, *b, nb_max, nb_dev, w.split, w.bits,
+                                                                  w.ic, *out, src_out_dev, ctx->dev_status);
         else
-            k_causal_write<false><<<(unsigned)ntiles, UWB, 0, s>>>(*a, na_max, na_dev, *b, nb_max, nb_dev, split, bits, ic,
-                                                                   *out, src_out_dev, ctx->dev_status);
+            k_causal_write<false><<<(unsigned)ntiles, UWB, 0, s>>>(*a, na_max, na_dev, *b, nb_max, nb_dev, w.split, w.bits,
+                                                                   w.ic, *out, src_out_dev, ctx->dev_status);
     }
     return check_launch(ctx);
 }

@@ -27,17 +27,15 @@
 //           change is one decision, the tile's first tag end.  cut[rep] is
 //           loaded only at a deciding position whose tomb-OR is 1, or may
 //           become 1 by the carry, and whose rep < n_cut.
-//   scan  : one workgroup.  The carry state is one bit (a tombstone seen in
-//           the open tag run), a tile's record the 2-entry function it applies
-//           to it plus both outcomes of its first tag end; composing functions
-//           is associative, so the carries into all tiles are a prefix scan --
-//           linear however many tiles one tag spans.  It patches the at most
-//           one affected emit / tomb bit and count per tile, scans the counts
-//           to offsets and stores the total.
-//   write : reads the bitmaps, stores the four fields of each emitting tuple
-//           at its rank, and the source index when asked (the walk back over
-//           equal-tag copies to the first one goes through global memory, as
-//           k_lww_write's does; LWW takes the tomb there).
+//   scan  : k_tile_scan<CmpCarry> (settile.hpp; LWW: <NoCarry>).  The carry
+//           state is one bit (a tombstone seen in the open tag run), a tile's
+//           record the 2-entry function it applies to it plus both outcomes of
+//           its first tag end; composing functions is associative, so the
+//           carries into all tiles are a prefix scan -- linear however many
+//           tiles one tag spans.  The scan patches the at most one affected
+//           emit / tomb bit and count per tile.
+//   write : k_tile_write (settile.hpp): the four fields of each emitting tuple
+//           at its rank, and the source index when asked.
 // LWW needs no carry: the last tuple of a key's run holds the key's maximal tag.
 //
 // The tuple count may stay on the device (n_dev): every kernel reads it, tiles
@@ -45,15 +43,11 @@
 // tuple, stores a count of ~0 and raises CRDT_DEV_RANGE.  No kernel reads a
 // tuple index at or past that length or before 0 -- the write pass checks every
 // bitmap position against it before its first load -- nor cut at or past n_cut.
-#include "common.hpp"
+#include "settile.hpp"
 
 namespace crdt {
 
-constexpr int CT = 2048;                 // tuples per tile
-constexpr int CB = 256;                  // threads per tile (4 waves)
-constexpr int CWW = CT / CB;             // 64-tuple mask words per wave (consecutive: 512 tuples)
-constexpr int CNW = CT / 64;             // bitmap words per tile
-constexpr uint32_t kCmpScanMax = 16384;  // tiles per scan round (16 per thread)
+constexpr int CT = kTile, CB = kTileB, CWW = kTileWW, CNW = kTileNW;   // tile, its threads, words per wave and tile
 
 // ---- carry records (OR-Set).  State s = a tombstone seen in the open tag run.
 //   bits 0-1   F: the state after the segment, per state before it
@@ -118,11 +112,22 @@ __device__ __forceinline__ uint32_t cmp_word_rec(uint64_t V, uint64_t ST, uint64
     return r;
 }
 
-// the call's tuple count: n_max, or the device count when it is in range
-__device__ __forceinline__ bool cmp_len(uint64_t n_max, const uint64_t *__restrict__ n_dev, uint64_t *n) {
-    *n = n_dev ? *n_dev : n_max;
-    return *n <= n_max;
-}
+// the scan's view of a record: F composes; the first tag end's emit and tomb are E and T at the carry, not at 0
+struct CmpCarry : PlainTiles {
+    static constexpr bool kHas = true;
+    static constexpr uint32_t kId = kCmpId, kStride = 2 * CNW, kEmit = 0, kAux = CNW;   // (`emit`, then `tomb`)
+    static __device__ __forceinline__ uint32_t part(uint32_t r) { return r & 3u; }
+    static __device__ __forceinline__ uint32_t then(uint32_t a, uint32_t b) { return cmp_fn_then(a, b); }
+    static __device__ __forceinline__ uint32_t seed(uint32_t) { return kCmpId; }
+    static __device__ __forceinline__ uint32_t enter(uint32_t p, uint32_t s) { return cmp_f(p, s); }
+    static __device__ __forceinline__ uint32_t step(uint32_t s, uint32_t r) { return cmp_f(r, s); }
+    static __device__ __forceinline__ uint32_t redecide(uint32_t r, uint32_t s) {
+        if (!((r & kCmpTE) && s != 0)) return 0;
+        const bool e0 = cmp_e(r, 0) != 0, e1 = cmp_e(r, s) != 0;
+        const bool t0 = e0 && cmp_t(r, 0) != 0, t1 = e1 && cmp_t(r, s) != 0;
+        return redo(cmp_pos(r), e0 != e1, t0 != t1, e1);
+    }
+};
 
 // ---------------------------------------------------------------- OR-Set count pass
 template <bool BITS>
@@ -132,7 +137,7 @@ __global__ __launch_bounds__(CB) void k_cmp_or_count(crdt_tuples T, uint64_t n_m
                                                      uint64_t *__restrict__ bits) {
     __shared__ uint32_t s_rec[CB / 64], s_cnt[CB / 64];
     uint64_t n;
-    if (!cmp_len(n_max, n_dev, &n)) return;
+    if (!tile_len(n_max, n_dev, &n)) return;
     const uint64_t t = blockIdx.x, tb = t * CT;
     if (tb >= n) return;                                 // (uniform; so n > 0 below)
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -241,7 +246,7 @@ __global__ __launch_bounds__(CB) void k_cmp_lww_count(crdt_tuples T, uint64_t n_
                                                       uint32_t *__restrict__ tcnt, uint64_t *__restrict__ bits) {
     __shared__ uint32_t s_cnt[CB / 64];
     uint64_t n;
-    if (!cmp_len(n_max, n_dev, &n)) return;
+    if (!tile_len(n_max, n_dev, &n)) return;
     const uint64_t t = blockIdx.x, tb = t * CT;
     if (tb >= n) return;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -316,188 +321,6 @@ __global__ __launch_bounds__(CB) void k_cmp_lww_count(crdt_tuples T, uint64_t n_
     }
 }
 
-// ---------------------------------------------------------------- carry + scan
-// One workgroup, rounds of up to kCmpScanMax tiles (k_read_scan's scheme, a
-// contiguous run of 16 tiles per thread): with rec, the carries into every
-// tile as a scan of the records' functions, the first tag end of each tile
-// re-decided under its carry (emit and tomb bit in bits, when given, and the
-// count); then the counts to offsets (ic, when given; ic[tiles] = the total)
-// and the total to *count.  bits holds bstride words per tile, the emit words
-// first, the tomb words CNW after them.
-__global__ __launch_bounds__(1024) void k_cmp_scan(uint64_t n_max, const uint64_t *__restrict__ n_dev,
-                                                   const uint32_t *__restrict__ tcnt, const uint32_t *__restrict__ rec,
-                                                   uint64_t *__restrict__ bits, uint32_t bstride,
-                                                   uint64_t *__restrict__ ic, uint64_t *__restrict__ count,
-                                                   uint32_t *__restrict__ err) {
-    constexpr int K = kCmpScanMax / 1024;
-    __shared__ uint32_t s_f[16];
-    __shared__ uint64_t s_c[16];
-    uint64_t n;
-    if (!cmp_len(n_max, n_dev, &n)) {
-        if (threadIdx.x == 0) {
-            *count = ~0ull;
-            atomicOr(err, CRDT_DEV_RANGE);
-        }
-        return;
-    }
-    const uint64_t nt = (n + CT - 1) / CT;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t state = 0;                                  // the carry into the round's first tile
-    uint64_t base = 0;
-    for (uint64_t c0 = 0; c0 < nt; c0 += kCmpScanMax) {
-        const uint64_t b = c0 + (uint64_t)threadIdx.x * K;
-        uint32_t v[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) v[q] = b + q < nt ? tcnt[b + q] : 0u;
-        if (rec) {
-            uint32_t rr[K], f = kCmpId;
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                rr[q] = b + q < nt ? rec[b + q] : kCmpId;
-                f = cmp_fn_then(f, rr[q] & 3u);
-            }
-            uint32_t x = f;                              // inclusive scan over the wave's threads
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = __shfl_up(x, o, 64);
-                if (lane >= o) x = cmp_fn_then(y, x);
-            }
-            if (lane == 63) s_f[w] = x;
-            uint32_t ex = __shfl_up(x, 1, 64);
-            if (lane == 0) ex = kCmpId;
-            __syncthreads();
-            uint32_t pre = kCmpId, tot = kCmpId;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if (q < w) pre = cmp_fn_then(pre, s_f[q]);
-                tot = cmp_fn_then(tot, s_f[q]);
-            }
-            uint32_t s = cmp_f(cmp_fn_then(pre, ex), state);
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                const uint32_t r = rr[q];
-                if (b + q < nt && (r & kCmpTE) && s != 0) {
-                    const bool e0 = cmp_e(r, 0) != 0, e1 = cmp_e(r, s) != 0;
-                    const bool t0 = e0 && cmp_t(r, 0) != 0, t1 = e1 && cmp_t(r, s) != 0;
-                    const uint32_t p = cmp_pos(r);
-                    if (e0 != e1) {
-                        if (bits) bits[(b + q) * bstride + (p >> 6)] ^= 1ull << (p & 63);
-                        v[q] += e1 ? 1u : 0xffffffffu;
-                    }
-                    if (bits && t0 != t1) bits[(b + q) * bstride + CNW + (p >> 6)] ^= 1ull << (p & 63);
-                }
-                s = cmp_f(r, s);
-            }
-            state = cmp_f(tot, state);
-        }
-        uint64_t sum = 0;
-#pragma unroll
-        for (int q = 0; q < K; ++q) sum += v[q];
-        uint64_t x = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_c[w] = x;
-        __syncthreads();
-        uint64_t run = base + x - sum, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            run += q < w ? s_c[q] : 0;
-            tot += s_c[q];
-        }
-        if (ic) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                if (b + q < nt) ic[b + q] = run;
-                run += v[q];
-            }
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (ic) ic[nt] = base;
-        *count = base;
-    }
-}
-
-// ---------------------------------------------------------------- write pass
-template <bool LWW, bool SRC>
-__global__ __launch_bounds__(CB) void k_cmp_write(crdt_tuples T, uint64_t n_max, const uint64_t *__restrict__ n_dev,
-                                                  const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
-                                                  crdt_tuples out, int64_t *__restrict__ src,
-                                                  uint32_t *__restrict__ err) {
-    constexpr int BS = LWW ? CNW : 2 * CNW;
-    uint64_t n;
-    if (!cmp_len(n_max, n_dev, &n)) return;
-    const uint64_t t = blockIdx.x, tb = t * CT;
-    if (tb >= n) return;
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // every wave holds the tile's words, lane w word w
-    const uint64_t wd = lane < CNW ? bits[t * BS + lane] : 0ull;
-    const uint64_t wt = !LWW && lane < CNW ? bits[t * BS + CNW + lane] : 0ull;
-    const uint32_t pc = (uint32_t)__popcll(wd);
-    uint32_t x = pc;
-#pragma unroll
-    for (int o = 1; o < CNW; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    const uint32_t ex = x - pc;
-    const uint64_t base = ic[t];
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < CWW; ++j) {
-        const int q = wv * CWW + j;
-        const uint64_t wq = (uint64_t)__shfl((unsigned long long)wd, q, 64);
-        const uint64_t tq = LWW ? 0ull : (uint64_t)__shfl((unsigned long long)wt, q, 64);
-        const uint32_t pq = __shfl(ex, q, 64);
-        if ((wq >> lane) & 1) {
-            const uint64_t i = tb + (uint64_t)q * 64 + lane;
-            const uint64_t at = base + pq + (uint32_t)__popcll(wq & ((1ull << lane) - 1));
-            if (!(i < n && at < n_max)) {                // (a bitmap of this call's count pass never fails this)
-                bad = true;
-                continue;
-            }
-            const uint64_t key = T.key[i], ts = T.ts[i];
-            const uint32_t rep = T.rep[i];
-            uint8_t tomb = LWW ? T.tomb[i] : (uint8_t)((tq >> lane) & 1);
-            uint64_t f = i;
-            if (LWW || SRC) {                            // the first copy of the tag: its index, LWW its tomb
-                const uint64_t p = i > 0 ? i - 1 : 0;
-                const uint64_t pk = T.key[p], pts = T.ts[p];
-                const uint32_t pr = T.rep[p];
-                if (i > 0 && pk == key && pts == ts && pr == rep) {
-                    f = p;
-                    while (f > 0 && T.key[f - 1] == key && T.ts[f - 1] == ts && T.rep[f - 1] == rep) --f;
-                    if (LWW) tomb = T.tomb[f];
-                }
-            }
-            out.key[at] = key;
-            out.ts[at] = ts;
-            out.rep[at] = rep;
-            out.tomb[at] = tomb;
-            if (SRC) src[at] = (int64_t)f;
-        }
-    }
-    if (bad) atomicOr(err, CRDT_DEV_RANGE);
-}
-
-static bool cmp_overlap(const void *a, size_t an, const void *b, size_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return an && bn && x < y + bn && y < x + an;
-}
-static bool cmp_misaligned(const crdt_tuples *t) {
-    return ((((uintptr_t)t->key | (uintptr_t)t->ts) & 7) | ((uintptr_t)t->rep & 3)) != 0;
-}
-// any field of t (n elements) overlaps [p, p + bytes)
-static bool cmp_tuples_overlap(const crdt_tuples *t, size_t n, const void *p, size_t bytes) {
-    return cmp_overlap(t->key, n * 8, p, bytes) || cmp_overlap(t->ts, n * 8, p, bytes) ||
-           cmp_overlap(t->rep, n * 4, p, bytes) || cmp_overlap(t->tomb, n, p, bytes);
-}
-
 }  // namespace crdt
 
 using namespace crdt;
@@ -511,50 +334,33 @@ extern "C" int crdt_set_compact(crdt_ctx *ctx, int mode, const crdt_tuples *t, s
     if (n_max >= (1ULL << 62) || n_cut >= (1ULL << 32)) return CRDT_E_RANGE;
     if ((n_cut && !cut_dev) || ((uintptr_t)cut_dev & 7)) return CRDT_E_INVAL;
     if (!out && src_out_dev) return CRDT_E_INVAL;
-    if (n_max && (!t->key || !t->ts || !t->rep || !t->tomb)) return CRDT_E_INVAL;
-    if (cmp_misaligned(t) || (out && cmp_misaligned(out)) || ((uintptr_t)src_out_dev & 7)) return CRDT_E_INVAL;
+    if (n_max && tuples_null(t)) return CRDT_E_INVAL;
+    if (tuples_misaligned(t) || (out && tuples_misaligned(out)) || ((uintptr_t)src_out_dev & 7)) return CRDT_E_INVAL;
     if (out && n_max) {
-        if (!out->key || !out->ts || !out->rep || !out->tomb) return CRDT_E_INVAL;
-        const void *of[4] = {out->key, out->ts, out->rep, out->tomb};
-        const size_t ow[4] = {8, 8, 4, 1};
-        for (int a = 0; a < 4; ++a) {
-            if (cmp_tuples_overlap(t, n_max, of[a], n_max * ow[a]) || cmp_overlap(cut_dev, n_cut * 8, of[a], n_max * ow[a]) ||
-                cmp_overlap(src_out_dev, src_out_dev ? n_max * 8 : 0, of[a], n_max * ow[a]))
-                return CRDT_E_INVAL;
-        }
-        if (src_out_dev && (cmp_tuples_overlap(t, n_max, src_out_dev, n_max * 8) ||
-                            cmp_overlap(cut_dev, n_cut * 8, src_out_dev, n_max * 8)))
+        if (tuples_null(out)) return CRDT_E_INVAL;
+        if (tuples_overlap(out, n_max, t, n_max) || tuples_overlap(out, n_max, cut_dev, n_cut * 8) ||
+            tuples_overlap(out, n_max, src_out_dev, n_max * 8) || tuples_overlap(t, n_max, src_out_dev, n_max * 8) ||
+            spans_overlap(cut_dev, n_cut * 8, src_out_dev, n_max * 8))
             return CRDT_E_INVAL;
     }
     const size_t ntiles = (n_max + CT - 1) / CT;
     if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;
-    const size_t need = 2 * Carve::round((ntiles + 1) * 4) + Carve::round((ntiles + 1) * 8) +
-                        Carve::round((ntiles * 2 * CNW + 1) * 8) + 1024;
-    rc = ws_reserve(ctx, need);
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, false, true, 2 * CNW);
     if (rc) return rc;
-    Carve w(ctx->ws);
-    uint32_t *tcnt = w.take<uint32_t>(ntiles + 1);
-    uint32_t *rec = w.take<uint32_t>(ntiles + 1);
-    uint64_t *ic = w.take<uint64_t>(ntiles + 1);
-    uint64_t *bits = w.take<uint64_t>(ntiles * 2 * CNW + 1);
     const bool lww = mode == CRDT_SET_LWW, wr = out != nullptr;
     const uint32_t nc = (uint32_t)n_cut;
     const hipStream_t s = ctx->stream;
     const unsigned g = (unsigned)ntiles;
     if (ntiles) {
-        if (lww && wr) k_cmp_lww_count<true><<<g, CB, 0, s>>>(*t, n_max, n_dev, cut_dev, nc, tcnt, bits);
-        else if (lww) k_cmp_lww_count<false><<<g, CB, 0, s>>>(*t, n_max, n_dev, cut_dev, nc, tcnt, bits);
-        else if (wr) k_cmp_or_count<true><<<g, CB, 0, s>>>(*t, n_max, n_dev, cut_dev, nc, tcnt, rec, bits);
-        else k_cmp_or_count<false><<<g, CB, 0, s>>>(*t, n_max, n_dev, cut_dev, nc, tcnt, rec, bits);
+        if (lww && wr) k_cmp_lww_count<true><<<g, CB, 0, s>>>(*t, n_max, n_dev, cut_dev, nc, w.tcnt, w.bits);
+        else if (lww) k_cmp_lww_count<false><<<g, CB, 0, s>>>(*t, n_max, n_dev, cut_dev, nc, w.tcnt, w.bits);
+        else if (wr) k_cmp_or_count<true><<<g, CB, 0, s>>>(*t, n_max, n_dev, cut_dev, nc, w.tcnt, w.rec, w.bits);
+        else k_cmp_or_count<false><<<g, CB, 0, s>>>(*t, n_max, n_dev, cut_dev, nc, w.tcnt, w.rec, w.bits);
     }
-    k_cmp_scan<<<1, 1024, 0, s>>>(n_max, n_dev, tcnt, lww ? nullptr : rec, wr ? bits : nullptr,
-                                  lww ? (uint32_t)CNW : (uint32_t)(2 * CNW), wr ? ic : nullptr, count, ctx->dev_status);
-    if (ntiles && wr) {
-        const bool sr = src_out_dev != nullptr;
-        if (lww && sr) k_cmp_write<true, true><<<g, CB, 0, s>>>(*t, n_max, n_dev, bits, ic, *out, src_out_dev, ctx->dev_status);
-        else if (lww) k_cmp_write<true, false><<<g, CB, 0, s>>>(*t, n_max, n_dev, bits, ic, *out, src_out_dev, ctx->dev_status);
-        else if (sr) k_cmp_write<false, true><<<g, CB, 0, s>>>(*t, n_max, n_dev, bits, ic, *out, src_out_dev, ctx->dev_status);
-        else k_cmp_write<false, false><<<g, CB, 0, s>>>(*t, n_max, n_dev, bits, ic, *out, src_out_dev, ctx->dev_status);
-    }
+    if (lww) w.scan<NoCarry<>>(ctx, n_max, n_dev, 0, nullptr, wr, count);
+    else w.scan<CmpCarry>(ctx, n_max, n_dev, 0, nullptr, wr, count);
+    if (ntiles && wr)
+        tile_write(lww, src_out_dev != nullptr, g, s, *t, n_max, n_dev, w.bits, w.ic, *out, src_out_dev, ctx->dev_status);
     return check_launch(ctx);
 }

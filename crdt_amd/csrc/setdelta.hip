@@ -17,8 +17,7 @@
 // (dst, src), dst first on an equal tag (LWW: on an equal key), every
 // decision taken at the LAST merged item of a tag run (LWW: key run) -- that
 // item is a src item exactly when src holds the tag (key):
-//   split : merge-path splits of every 2048-item tile (the 16-ary search of
-//           k_or_split / k_lww_split, the lengths read on the device);
+//   split : k_mp_split (settile.hpp), side a = dst, by keys alone for LWW;
 //   count : per tile both runs staged in LDS (plain loads, clamped to each
 //           side's length) and merged, 512 threads x 4 items.  OR-Set: a
 //           thread carries the open tag run's state (dst copy seen, dst
@@ -31,29 +30,27 @@
 //           ts / rep are read only there.  Output: bitmaps in merged order
 //           (`iss`: a src item, `emit`, OR-Set `tomb`: the emitted tomb), the
 //           tile's count and record;
-//   scan  : one workgroup, rounds of 16384 tiles: the carries into all tiles
-//           as a scan of the records (linear however many tiles a tag spans),
-//           each tile's first run end re-decided under its carry, the counts
-//           to offsets, the total to *count;
-//   write : (out != NULL) one output per lane, by rank: the rank's emit bit is
-//           selected from the tile's bitmap, its src index is a prefix
-//           popcount of `iss`; the four fields stored at the rank (LWW: the
-//           tomb of the first copy of the tag, a walk back over src).
+//   scan  : k_tile_scan<DeltaCarry> (settile.hpp; LWW: <NoCarry>): the records
+//           scan as they are, each tile's first run end, when a src item, is
+//           re-decided with the carry's bits ORed into its run's own;
+//   write : (out != NULL) one output per lane, by rank (rank_words /
+//           rank_select, settile.hpp): its src index is the count of src items
+//           before it; the four fields stored at the rank (LWW: the tomb of
+//           the first copy of the tag, a walk back over src).
 //
 // Either length may stay on the device.  A value past its n_max touches no
 // tuple, stores a count of ~0 and raises CRDT_DEV_RANGE; no kernel reads an
 // index at or past min(*n_dev, n_max) of its side, or before 0.
-#include "scan.hpp"
+#include "settile.hpp"
 
 namespace crdt {
 
-constexpr int DT = 2048;                  // merge items per tile
+constexpr int DT = kTile;                 // merge items per tile
 constexpr int DCB = 512;                  // count pass threads
 constexpr int DNI = DT / DCB;             // merge items per count thread
-constexpr int DNW = DT / 64;              // words per tile and bitmap
+constexpr int DNW = kTileNW;              // words per tile and bitmap
 constexpr int DWB = 256;                  // write pass threads (one output each per round)
 constexpr int DCAP = DT + 4;              // staged slots: each side's run, the element before and the one after it
-constexpr uint32_t kDeltaScanMax = 16384; // tiles per scan round (16 per thread)
 
 // ---- the open tag run's state and a segment's record (OR-Set)
 constexpr uint32_t kHasD = 1, kTorD = 2, kTorS = 4;   // dst copy seen / dst tomb-OR / src tomb-OR
@@ -64,67 +61,30 @@ constexpr uint32_t kEnd = 8;                          // the segment holds a run
 __device__ __forceinline__ uint32_t st_then(uint32_t a, uint32_t b) { return (b & kEnd) ? b : (a | b); }
 __device__ __forceinline__ bool st_ships(uint32_t s) { return !(s & kHasD) || ((s & kTorS) && !(s & kTorD)); }
 
-// both lengths, each n_max or its device count; false when either is out of range
-__device__ __forceinline__ bool delta_len(uint64_t ns_max, const uint64_t *__restrict__ ns_dev, uint64_t nd_max,
-                                          const uint64_t *__restrict__ nd_dev, uint64_t *ns, uint64_t *nd) {
-    *ns = ns_dev ? *ns_dev : ns_max;
-    *nd = nd_dev ? *nd_dev : nd_max;
-    return *ns <= ns_max && *nd <= nd_max;
-}
 // tiles of the call: none without a src tuple
 __device__ __forceinline__ uint64_t delta_tiles(uint64_t ns, uint64_t nd) { return ns ? (ns + nd + DT - 1) / DT : 0; }
-
-// D[i] <= S[j] in merge order (LWW: keys only; OR-Set: ts / rep read only on a tie)
-template <bool LWW>
-__device__ __forceinline__ bool d_le(const crdt_tuples &D, uint64_t i, const crdt_tuples &S, uint64_t j) {
-    const uint64_t kd = D.key[i], ks = S.key[j];
-    if (LWW || kd != ks) return kd <= ks;
-    const uint64_t td = D.ts[i], ts = S.ts[j];
-    if (td != ts) return td < ts;
-    return D.rep[i] <= S.rep[j];
-}
-
-// ---------------------------------------------------------------- split
-// split[t] = dst elements among the first min(t DT, n) merged items, t = 0 ..
-// tiles: one 16-lane group per diagonal, four per wave.
-template <bool LWW>
-__global__ __launch_bounds__(256) void k_delta_split(crdt_tuples S, uint64_t ns_max, const uint64_t *__restrict__ ns_dev,
-                                                     crdt_tuples D, uint64_t nd_max, const uint64_t *__restrict__ nd_dev,
-                                                     uint64_t *__restrict__ split) {
-    uint64_t ns, nd;
-    if (!delta_len(ns_max, ns_dev, nd_max, nd_dev, &ns, &nd)) return;
-    const uint64_t ntiles = delta_tiles(ns, nd);
-    if (ntiles == 0) return;
-    const int lane = threadIdx.x & 63, grp = lane >> 4, gl = lane & 15;
-    const uint64_t t = ((((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6) << 2) + (uint64_t)grp;
-    const uint64_t n = ns + nd;
-    const uint64_t d = t < ntiles ? t * DT : n;
-    uint64_t lo = d > ns ? d - ns : 0, hi = d < nd ? d : nd;
-    bool done = t > ntiles || hi <= lo;
-    // P(i) = D[i] <= S[d-1-i]: true below the split, false from it
-    while (__ballot(!done)) {
-        const uint64_t span = hi - lo;
-        const bool small = span <= 16;
-        const uint64_t c = small ? lo + (uint64_t)gl : lo + ((uint64_t)gl * span) / 16;
-        const bool valid = !done && (small ? (uint64_t)gl < span : true);
-        const bool p = valid && d_le<LWW>(D, c, S, d - 1 - c);
-        const unsigned m = (unsigned)((__ballot(p) >> (grp * 16)) & 0xFFFF);
-        const unsigned cnt = (unsigned)__popc(m);
-        if (!done) {
-            if (small) {
-                lo += cnt;
-                done = true;
-            } else {
-                const uint64_t nlo = cnt > 0 ? lo + (((uint64_t)(cnt - 1)) * span) / 16 + 1 : lo;
-                const uint64_t nhi = cnt < 16 ? lo + ((uint64_t)cnt * span) / 16 : hi;
-                lo = nlo;
-                hi = nhi;
-                done = hi <= lo;
-            }
-        }
+// the shared passes' view: side a = dst (it wins ties), side b = src
+struct DeltaTiles {
+    static __device__ __forceinline__ uint64_t tiles(uint64_t nd, uint64_t ns) { return delta_tiles(ns, nd); }
+};
+// the scan's view of a record: the state scans as it is; the first run end,
+// when a src item, is re-decided with the carry's bits ORed into its run's own
+struct DeltaCarry : DeltaTiles {
+    static constexpr bool kHas = true;
+    static constexpr uint32_t kId = 0, kStride = 3 * DNW, kEmit = DNW, kAux = 2 * DNW;   // (`iss`, `emit`, `tomb`)
+    static __device__ __forceinline__ uint32_t part(uint32_t r) { return r & 0xfu; }
+    static __device__ __forceinline__ uint32_t then(uint32_t a, uint32_t b) { return st_then(a, b); }
+    static __device__ __forceinline__ uint32_t seed(uint32_t s) { return s; }
+    static __device__ __forceinline__ uint32_t enter(uint32_t p, uint32_t) { return p; }
+    static __device__ __forceinline__ uint32_t step(uint32_t s, uint32_t r) { return st_then(s, r & 0xfu); }
+    static __device__ __forceinline__ uint32_t redecide(uint32_t r, uint32_t s) {
+        if (!((r & kEnd) && (r & 0x80u))) return 0;      // (a tile past the last holds no end)
+        const uint32_t own = (r >> 4) & 7u, all = own | (s & 7u);
+        const bool e0 = st_ships(own), e1 = st_ships(all);
+        const bool t0 = e0 && (own & kTorS), t1 = e1 && (all & kTorS);
+        return redo(r >> 16, e0 != e1, t0 != t1, e1);
     }
-    if (gl == 0 && t <= ntiles) split[t] = lo;
-}
+};
 
 // ---------------------------------------------------------------- count
 template <bool LWW, bool BITS>
@@ -139,7 +99,7 @@ __global__ __launch_bounds__(DCB) void k_delta_count(crdt_tuples S, uint64_t ns_
     __shared__ uint8_t sm[LWW ? 4 : DCAP];
     __shared__ uint32_t s_w[DCB / 64], s_c[DCB / 64], s_first;
     uint64_t ns, nd;
-    if (!delta_len(ns_max, ns_dev, nd_max, nd_dev, &ns, &nd)) return;
+    if (!tile_len(ns_max, ns_dev, nd_max, nd_dev, &ns, &nd)) return;
     const uint64_t t = blockIdx.x;
     if (t >= delta_tiles(ns, nd)) return;                // (uniform)
     const uint64_t n = ns + nd, d0 = t * DT, d1 = d0 + DT < n ? d0 + DT : n;
@@ -309,112 +269,6 @@ __global__ __launch_bounds__(DCB) void k_delta_count(crdt_tuples S, uint64_t ns_
     }
 }
 
-// ---------------------------------------------------------------- carry + scan
-// One workgroup, rounds of up to kDeltaScanMax tiles (a contiguous run of 16
-// tiles per thread): with rec, the carry into every tile as a scan of the
-// records, the first run end of each tile re-decided under its carry (emit
-// and tomb bits, when given, and the count); then the counts to offsets (ic,
-// when given; ic[tiles] = the total) and the total to *count.
-__global__ __launch_bounds__(1024) void k_delta_scan(uint64_t ns_max, const uint64_t *__restrict__ ns_dev,
-                                                     uint64_t nd_max, const uint64_t *__restrict__ nd_dev,
-                                                     const uint32_t *__restrict__ tcnt, const uint32_t *__restrict__ rec,
-                                                     uint64_t *__restrict__ bits, uint64_t *__restrict__ ic,
-                                                     uint64_t *__restrict__ count, uint32_t *__restrict__ err) {
-    constexpr int K = kDeltaScanMax / 1024;
-    __shared__ uint32_t s_f[16];
-    __shared__ uint64_t s_c[16];
-    uint64_t ns, nd;
-    if (!delta_len(ns_max, ns_dev, nd_max, nd_dev, &ns, &nd)) {
-        if (threadIdx.x == 0) {
-            *count = ~0ull;
-            atomicOr(err, CRDT_DEV_RANGE);
-        }
-        return;
-    }
-    const uint64_t nt = delta_tiles(ns, nd);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t state = 0;                                  // the carry into the round's first tile
-    uint64_t base = 0;
-    for (uint64_t c0 = 0; c0 < nt; c0 += kDeltaScanMax) {
-        const uint64_t b = c0 + (uint64_t)threadIdx.x * K;
-        uint32_t v[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) v[q] = b + q < nt ? tcnt[b + q] : 0u;
-        if (rec) {
-            uint32_t rr[K], f = 0;
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                rr[q] = b + q < nt ? rec[b + q] : 0u;
-                f = st_then(f, rr[q] & 0xfu);
-            }
-            uint32_t x = f;                              // inclusive scan over the wave's threads
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = __shfl_up(x, o, 64);
-                if (lane >= o) x = st_then(y, x);
-            }
-            if (lane == 63) s_f[w] = x;
-            uint32_t ex = __shfl_up(x, 1, 64);
-            if (lane == 0) ex = 0;
-            __syncthreads();
-            uint32_t pre = state, tot = state;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if (q < w) pre = st_then(pre, s_f[q]);
-                tot = st_then(tot, s_f[q]);
-            }
-            uint32_t s = st_then(pre, ex);
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                const uint32_t r = rr[q];
-                if ((r & kEnd) && (r & 0x80u)) {         // (a tile past nt holds no end)
-                    const uint32_t own = (r >> 4) & 7u, all = own | (s & 7u);
-                    const bool e0 = st_ships(own), e1 = st_ships(all);
-                    const bool t0 = e0 && (own & kTorS), t1 = e1 && (all & kTorS);
-                    const uint32_t p = r >> 16;
-                    if (e0 != e1) {
-                        if (bits) bits[(b + q) * (3 * DNW) + DNW + (p >> 6)] ^= 1ull << (p & 63);
-                        v[q] += e1 ? 1u : 0xffffffffu;
-                    }
-                    if (bits && t0 != t1) bits[(b + q) * (3 * DNW) + 2 * DNW + (p >> 6)] ^= 1ull << (p & 63);
-                }
-                s = st_then(s, r & 0xfu);
-            }
-            state = tot;
-        }
-        uint64_t sum = 0;
-#pragma unroll
-        for (int q = 0; q < K; ++q) sum += v[q];
-        uint64_t x = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_c[w] = x;
-        __syncthreads();
-        uint64_t run = base + x - sum, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            run += q < w ? s_c[q] : 0;
-            tot += s_c[q];
-        }
-        if (ic) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                if (b + q < nt) ic[b + q] = run;
-                run += v[q];
-            }
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (ic) ic[nt] = base;
-        *count = base;
-    }
-}
-
 // ---------------------------------------------------------------- write pass
 template <bool LWW>
 __global__ __launch_bounds__(DWB) void k_delta_write(crdt_tuples S, uint64_t ns_max, const uint64_t *__restrict__ ns_dev,
@@ -423,27 +277,14 @@ __global__ __launch_bounds__(DWB) void k_delta_write(crdt_tuples S, uint64_t ns_
                                                      const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
                                                      crdt_tuples out, uint32_t *__restrict__ err) {
     uint64_t ns, nd;
-    if (!delta_len(ns_max, ns_dev, nd_max, nd_dev, &ns, &nd)) return;
+    if (!tile_len(ns_max, ns_dev, nd_max, nd_dev, &ns, &nd)) return;
     const uint64_t t = blockIdx.x;
     if (t >= delta_tiles(ns, nd)) return;
     const int lane = threadIdx.x & 63;
     const uint64_t *b = bits + t * (3 * DNW);
-    // every wave holds the tile's words, lane w word w, and their exclusive prefix counts
-    const uint64_t ws = lane < DNW ? b[lane] : 0ull, we = lane < DNW ? b[DNW + lane] : 0ull;
+    const RankWords k = rank_words(b, lane);              // `iss`, `emit` and their prefix counts
     const uint64_t wt = !LWW && lane < DNW ? b[2 * DNW + lane] : 0ull;
-    const uint32_t ps = (uint32_t)__popcll(ws), pe = (uint32_t)__popcll(we);
-    uint32_t xs = ps, xe = pe;
-#pragma unroll
-    for (int o = 1; o < DNW; o <<= 1) {
-        const uint32_t ys = __shfl_up(xs, o, 64), ye = __shfl_up(xe, o, 64);
-        if (lane >= o) {
-            xs += ys;
-            xe += ye;
-        }
-    }
-    const uint32_t ne = (uint32_t)__builtin_amdgcn_readlane((int)xe, DNW - 1);   // the tile's outputs
-    xs -= ps;
-    xe -= pe;
+    const uint32_t ne = k.ne;
     const uint64_t j0 = t * DT - split[t], base = ic[t];
     bool bad = false;
     // one output per thread and round, by rank: every lane of a wave loads and
@@ -451,25 +292,11 @@ __global__ __launch_bounds__(DWB) void k_delta_write(crdt_tuples S, uint64_t ns_
     for (uint32_t r0 = 0; r0 < ne; r0 += DWB) {          // (uniform: the shuffles below read every word's lane)
         const bool valid = r0 + threadIdx.x < ne;
         const uint32_t r = valid ? r0 + threadIdx.x : ne - 1;
-        int w = 0;                                       // the last word with xe <= r: the one holding output r
-#pragma unroll
-        for (int o = DNW / 2; o > 0; o >>= 1)
-            if (__shfl(xe, w + o, 64) <= r) w += o;
-        const uint64_t qs = (uint64_t)__shfl((unsigned long long)ws, w, 64);
-        const uint64_t qe = (uint64_t)__shfl((unsigned long long)we, w, 64);
-        const uint64_t qt = LWW ? 0ull : (uint64_t)__shfl((unsigned long long)wt, w, 64);
-        uint32_t k = r - __shfl(xe, w, 64), pos = 0;     // its set bit of qe, counted from bit 0
-        uint64_t m = qe;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t c = (uint32_t)__popcll(m & ((1ull << o) - 1));
-            if (k >= c) {
-                k -= c;
-                m >>= o;
-                pos += o;
-            }
-        }
-        const uint64_t i = j0 + __shfl(xs, w, 64) + (uint32_t)__popcll(qs & ((1ull << pos) - 1));   // the src item's index
+        const RankHit h = rank_select(k, r);
+        const uint64_t qs = h.qb, qe = h.qe;
+        const uint64_t qt = LWW ? 0ull : (uint64_t)__shfl((unsigned long long)wt, h.w, 64);
+        const uint32_t pos = h.pos;
+        const uint64_t i = j0 + h.nb;                    // the src item's index
         const uint64_t at = base + r;
         if (!valid) continue;
         // (the bitmaps of this call's count pass never fail this)
@@ -500,23 +327,6 @@ __global__ __launch_bounds__(DWB) void k_delta_write(crdt_tuples S, uint64_t ns_
     if (bad) atomicOr(err, CRDT_DEV_RANGE);
 }
 
-static bool delta_overlap(const void *a, size_t an, const void *b, size_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return an && bn && x < y + bn && y < x + an;
-}
-static bool delta_misaligned(const crdt_tuples *t) {
-    return ((((uintptr_t)t->key | (uintptr_t)t->ts) & 7) | ((uintptr_t)t->rep & 3)) != 0;
-}
-// any field of o (no elements) overlaps any field of i (ni elements)
-static bool delta_tuples_overlap(const crdt_tuples *o, size_t no, const crdt_tuples *i, size_t ni) {
-    const void *of[4] = {o->key, o->ts, o->rep, o->tomb}, *inf[4] = {i->key, i->ts, i->rep, i->tomb};
-    const size_t w[4] = {8, 8, 4, 1};
-    for (int a = 0; a < 4; ++a)
-        for (int b = 0; b < 4; ++b)
-            if (delta_overlap(of[a], no * w[a], inf[b], ni * w[b])) return true;
-    return false;
-}
-
 }  // namespace crdt
 
 using namespace crdt;
@@ -528,50 +338,42 @@ extern "C" int crdt_set_delta(crdt_ctx *ctx, int mode, const crdt_tuples *src, s
     if (rc) return rc;
     if (!src || !dst || !count || (mode != CRDT_SET_LWW && mode != CRDT_SET_ORSET)) return CRDT_E_INVAL;
     if (ns_max >= (1ULL << 62) || nd_max >= (1ULL << 62)) return CRDT_E_RANGE;
-    if (ns_max && (!src->key || !src->ts || !src->rep || !src->tomb)) return CRDT_E_INVAL;
-    if (nd_max && (!dst->key || !dst->ts || !dst->rep || !dst->tomb)) return CRDT_E_INVAL;
-    if (delta_misaligned(src) || delta_misaligned(dst) || (out && delta_misaligned(out))) return CRDT_E_INVAL;
+    if (ns_max && tuples_null(src)) return CRDT_E_INVAL;
+    if (nd_max && tuples_null(dst)) return CRDT_E_INVAL;
+    if (tuples_misaligned(src) || tuples_misaligned(dst) || (out && tuples_misaligned(out))) return CRDT_E_INVAL;
     if (out && ns_max) {
-        if (!out->key || !out->ts || !out->rep || !out->tomb) return CRDT_E_INVAL;
-        if (delta_tuples_overlap(out, ns_max, src, ns_max) || delta_tuples_overlap(out, ns_max, dst, nd_max))
-            return CRDT_E_INVAL;
+        if (tuples_null(out)) return CRDT_E_INVAL;
+        if (tuples_overlap(out, ns_max, src, ns_max) || tuples_overlap(out, ns_max, dst, nd_max)) return CRDT_E_INVAL;
     }
     const size_t ntiles = ns_max ? (ns_max + nd_max + DT - 1) / DT : 0;
     if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;
-    const size_t need = Carve::round((ntiles + 2) * 8) + 2 * Carve::round((ntiles + 1) * 4) +
-                        Carve::round((ntiles + 1) * 8) + Carve::round((ntiles * 3 * DNW + 1) * 8) + 1280;
-    rc = ws_reserve(ctx, need);
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, true, true, 3 * DNW);
     if (rc) return rc;
-    Carve w(ctx->ws);
-    uint64_t *split = w.take<uint64_t>(ntiles + 2);
-    uint32_t *tcnt = w.take<uint32_t>(ntiles + 1);
-    uint32_t *rec = w.take<uint32_t>(ntiles + 1);
-    uint64_t *ic = w.take<uint64_t>(ntiles + 1);
-    uint64_t *bits = w.take<uint64_t>(ntiles * 3 * DNW + 1);
     const bool lww = mode == CRDT_SET_LWW, wr = out != nullptr;
     const hipStream_t s = ctx->stream;
+    const crdt_tuples &S = *src, &D = *dst;
     if (ntiles) {
-        const unsigned g = (unsigned)ntiles, gs = (unsigned)((ntiles + 1 + 15) / 16);   // 16 diagonals per split workgroup
-        if (lww) k_delta_split<true><<<gs, 256, 0, s>>>(*src, ns_max, ns_dev, *dst, nd_max, nd_dev, split);
-        else k_delta_split<false><<<gs, 256, 0, s>>>(*src, ns_max, ns_dev, *dst, nd_max, nd_dev, split);
+        const unsigned g = (unsigned)ntiles, gs = mp_split_grid(ntiles);
+        if (lww) k_mp_split<DT, TupleLe<true>, DeltaTiles><<<gs, 256, 0, s>>>(D, nd_max, nd_dev, S, ns_max, ns_dev, w.split);
+        else k_mp_split<DT, TupleLe<false>, DeltaTiles><<<gs, 256, 0, s>>>(D, nd_max, nd_dev, S, ns_max, ns_dev, w.split);
         if (lww && wr)
-            k_delta_count<true, true><<<g, DCB, 0, s>>>(*src, ns_max, ns_dev, *dst, nd_max, nd_dev, split, tcnt, rec, bits);
+            k_delta_count<true, true><<<g, DCB, 0, s>>>(S, ns_max, ns_dev, D, nd_max, nd_dev, w.split, w.tcnt, w.rec, w.bits);
         else if (lww)
-            k_delta_count<true, false><<<g, DCB, 0, s>>>(*src, ns_max, ns_dev, *dst, nd_max, nd_dev, split, tcnt, rec, bits);
+            k_delta_count<true, false><<<g, DCB, 0, s>>>(S, ns_max, ns_dev, D, nd_max, nd_dev, w.split, w.tcnt, w.rec, w.bits);
         else if (wr)
-            k_delta_count<false, true><<<g, DCB, 0, s>>>(*src, ns_max, ns_dev, *dst, nd_max, nd_dev, split, tcnt, rec, bits);
+            k_delta_count<false, true><<<g, DCB, 0, s>>>(S, ns_max, ns_dev, D, nd_max, nd_dev, w.split, w.tcnt, w.rec, w.bits);
         else
-            k_delta_count<false, false><<<g, DCB, 0, s>>>(*src, ns_max, ns_dev, *dst, nd_max, nd_dev, split, tcnt, rec, bits);
+            k_delta_count<false, false><<<g, DCB, 0, s>>>(S, ns_max, ns_dev, D, nd_max, nd_dev, w.split, w.tcnt, w.rec, w.bits);
     }
-    k_delta_scan<<<1, 1024, 0, s>>>(ns_max, ns_dev, nd_max, nd_dev, tcnt, lww ? nullptr : rec, wr ? bits : nullptr,
-                                    wr ? ic : nullptr, count, ctx->dev_status);
+    if (lww) w.scan<NoCarry<DeltaTiles>>(ctx, nd_max, nd_dev, ns_max, ns_dev, wr, count);
+    else w.scan<DeltaCarry>(ctx, nd_max, nd_dev, ns_max, ns_dev, wr, count);
     if (ntiles && wr) {
+        const unsigned g = (unsigned)ntiles;
         if (lww)
-            k_delta_write<true><<<(unsigned)ntiles, DWB, 0, s>>>(*src, ns_max, ns_dev, nd_max, nd_dev, split, bits, ic,
-                                                                *out, ctx->dev_status);
+            k_delta_write<true><<<g, DWB, 0, s>>>(S, ns_max, ns_dev, nd_max, nd_dev, w.split, w.bits, w.ic, *out, ctx->dev_status);
         else
-            k_delta_write<false><<<(unsigned)ntiles, DWB, 0, s>>>(*src, ns_max, ns_dev, nd_max, nd_dev, split, bits, ic,
-                                                                 *out, ctx->dev_status);
+            k_delta_write<false><<<g, DWB, 0, s>>>(S, ns_max, ns_dev, nd_max, nd_dev, w.split, w.bits, w.ic, *out, ctx->dev_status);
     }
     return check_launch(ctx);
 }

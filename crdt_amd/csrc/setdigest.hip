@@ -46,33 +46,22 @@
 //            segmented shuffle scan per word), one 64-bit global atomicAdd pair
 //            per wave (word) and bucket run.
 //   select : compaction with another drop predicate (the bucket is unflagged):
-//            count (emit / tomb bitmaps and tile counts) / scan (one workgroup,
-//            counts to offsets) / write (the fields of each emitting tuple at
-//            its rank; LWW's tomb and the source index from the walk back to
-//            the tag's first copy).  The tomb is settled in the count pass, so
-//            the scan carries counts alone.
-// The kernels are this file's own: crdt_set_compact's stay byte-identical.
+//            count (emit / tomb bitmaps and tile counts), then the scan and the
+//            write pass of settile.hpp: k_tile_scan<NoCarry> -- the tomb is
+//            settled in the count pass, so the scan carries counts alone --
+//            and crdt_set_compact's k_tile_write.
 //
 // The tuple count may stay on the device (n_dev) exactly as in setcompact.hip:
 // tiles at or past min(*n_dev, n_max) do nothing; *n_dev > n_max touches no
 // tuple and raises CRDT_DEV_RANGE (digest: every entry of both outputs ~0;
 // select: a count of ~0).  No kernel reads a tuple at or past that length or
 // before 0, a splitter at or past m, or a flag at or past m + 1.
-#include "common.hpp"
+#include "settile.hpp"
 
 namespace crdt {
 
-constexpr int GT = 2048;                 // tuples per tile
-constexpr int GB = 256;                  // threads per tile (4 waves)
-constexpr int GWW = GT / GB;             // 64-tuple mask words per wave (consecutive: 512 tuples)
-constexpr int GNW = GT / 64;             // bitmap words per tile
-constexpr uint32_t kDigScanMax = 16384;  // tiles per scan round (16 per thread)
+constexpr int GT = kTile, GB = kTileB, GWW = kTileWW, GNW = kTileNW;   // tile, its threads, words per wave and tile
 constexpr size_t kDigMaxSplit = (size_t)1 << 24;
-
-__device__ __forceinline__ bool dig_len(uint64_t n_max, const uint64_t *__restrict__ n_dev, uint64_t *n) {
-    *n = n_dev ? *n_dev : n_max;
-    return *n <= n_max;
-}
 
 __device__ __forceinline__ uint64_t dig_hash(uint64_t key, uint64_t ts, uint32_t rep, uint32_t tomb) {
     return splitmix64(splitmix64(splitmix64(key) ^ ts) ^ (((uint64_t)rep << 1) | (uint64_t)(tomb & 1u)));
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(256) void k_dig_init(uint64_t n_max, const uint64_t
                                                   uint64_t *__restrict__ hash, uint64_t *__restrict__ count,
                                                   uint32_t *__restrict__ err) {
     uint64_t n;
-    const bool ok = dig_len(n_max, n_dev, &n);
+    const bool ok = tile_len(n_max, n_dev, &n);
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < m1) {
         hash[i] = ok ? 0ull : ~0ull;
@@ -220,7 +209,7 @@ __global__ __launch_bounds__(GB) void k_dig_digest(crdt_tuples T, uint64_t n_max
                                                    const uint64_t *__restrict__ sp, uint32_t m,
                                                    uint64_t *__restrict__ hash, uint64_t *__restrict__ count) {
     uint64_t n;
-    if (!dig_len(n_max, n_dev, &n)) return;
+    if (!tile_len(n_max, n_dev, &n)) return;
     const uint64_t tb = (uint64_t)blockIdx.x * GT;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint64_t i0 = tb + (uint64_t)wv * (64 * GWW);
@@ -311,7 +300,7 @@ __global__ __launch_bounds__(GB) void k_sel_count(crdt_tuples T, uint64_t n_max,
     constexpr int BS = LWW ? GNW : 2 * GNW;
     __shared__ uint32_t s_cnt[GB / 64];
     uint64_t n;
-    if (!dig_len(n_max, n_dev, &n)) return;
+    if (!tile_len(n_max, n_dev, &n)) return;
     const uint64_t t = blockIdx.x, tb = t * GT;
     if (tb >= n) return;                                     // (uniform)
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -354,146 +343,13 @@ __global__ __launch_bounds__(GB) void k_sel_count(crdt_tuples T, uint64_t n_max,
     }
 }
 
-// ---------------------------------------------------------------- select: scan
-// One workgroup, rounds of up to kDigScanMax tiles (a contiguous run of 16
-// tiles per thread): the tile counts to offsets (ic, when given; ic[tiles] =
-// the total) and the total to *count.
-__global__ __launch_bounds__(1024) void k_sel_scan(uint64_t n_max, const uint64_t *__restrict__ n_dev,
-                                                   const uint32_t *__restrict__ tcnt, uint64_t *__restrict__ ic,
-                                                   uint64_t *__restrict__ count, uint32_t *__restrict__ err) {
-    constexpr int K = kDigScanMax / 1024;
-    __shared__ uint64_t s_c[16];
-    uint64_t n;
-    if (!dig_len(n_max, n_dev, &n)) {
-        if (threadIdx.x == 0) {
-            *count = ~0ull;
-            atomicOr(err, CRDT_DEV_RANGE);
-        }
-        return;
-    }
-    const uint64_t nt = (n + GT - 1) / GT;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t base = 0;
-    for (uint64_t c0 = 0; c0 < nt; c0 += kDigScanMax) {
-        const uint64_t b = c0 + (uint64_t)threadIdx.x * K;
-        uint32_t v[K];
-        uint64_t sum = 0;
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-            v[q] = b + q < nt ? tcnt[b + q] : 0u;
-            sum += v[q];
-        }
-        uint64_t x = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_c[w] = x;
-        __syncthreads();
-        uint64_t run = base + x - sum, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            run += q < w ? s_c[q] : 0;
-            tot += s_c[q];
-        }
-        if (ic) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                if (b + q < nt) ic[b + q] = run;
-                run += v[q];
-            }
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (ic) ic[nt] = base;
-        *count = base;
-    }
-}
-
-// ---------------------------------------------------------------- select: write pass
-template <bool LWW, bool SRC>
-__global__ __launch_bounds__(GB) void k_sel_write(crdt_tuples T, uint64_t n_max, const uint64_t *__restrict__ n_dev,
-                                                  const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
-                                                  crdt_tuples out, int64_t *__restrict__ src,
-                                                  uint32_t *__restrict__ err) {
-    constexpr int BS = LWW ? GNW : 2 * GNW;
-    uint64_t n;
-    if (!dig_len(n_max, n_dev, &n)) return;
-    const uint64_t t = blockIdx.x, tb = t * GT;
-    if (tb >= n) return;
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // every wave holds the tile's words, lane w word w
-    const uint64_t wd = lane < GNW ? bits[t * BS + lane] : 0ull;
-    const uint64_t wt = !LWW && lane < GNW ? bits[t * BS + GNW + lane] : 0ull;
-    const uint32_t pc = (uint32_t)__popcll(wd);
-    uint32_t x = pc;
-#pragma unroll
-    for (int o = 1; o < GNW; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    const uint32_t ex = x - pc;
-    const uint64_t base = ic[t];
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < GWW; ++j) {
-        const int q = wv * GWW + j;
-        const uint64_t wq = (uint64_t)__shfl((unsigned long long)wd, q, 64);
-        const uint64_t tq = LWW ? 0ull : (uint64_t)__shfl((unsigned long long)wt, q, 64);
-        const uint32_t pq = __shfl(ex, q, 64);
-        if ((wq >> lane) & 1) {
-            const uint64_t i = tb + (uint64_t)q * 64 + lane;
-            const uint64_t at = base + pq + (uint32_t)__popcll(wq & ((1ull << lane) - 1));
-            if (!(i < n && at < n_max)) {                    // (a bitmap of this call's count pass never fails this)
-                bad = true;
-                continue;
-            }
-            const uint64_t key = T.key[i], ts = T.ts[i];
-            const uint32_t rep = T.rep[i];
-            uint8_t tomb = LWW ? T.tomb[i] : (uint8_t)((tq >> lane) & 1);
-            uint64_t f = i;
-            if (LWW || SRC) {                                // the first copy of the tag: its index, LWW its tomb
-                const uint64_t p = i > 0 ? i - 1 : 0;
-                const uint64_t pk = T.key[p], pts = T.ts[p];
-                const uint32_t pr = T.rep[p];
-                if (i > 0 && pk == key && pts == ts && pr == rep) {
-                    f = p;
-                    while (f > 0 && T.key[f - 1] == key && T.ts[f - 1] == ts && T.rep[f - 1] == rep) --f;
-                    if (LWW) tomb = T.tomb[f];
-                }
-            }
-            out.key[at] = key;
-            out.ts[at] = ts;
-            out.rep[at] = rep;
-            out.tomb[at] = tomb;
-            if (SRC) src[at] = (int64_t)f;
-        }
-    }
-    if (bad) atomicOr(err, CRDT_DEV_RANGE);
-}
-
-static bool dig_overlap(const void *a, size_t an, const void *b, size_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && an && bn && x < y + bn && y < x + an;
-}
-static bool dig_misaligned(const crdt_tuples *t) {
-    return ((((uintptr_t)t->key | (uintptr_t)t->ts) & 7) | ((uintptr_t)t->rep & 3)) != 0;
-}
-// any field of t (n elements) overlaps [p, p + bytes)
-static bool dig_tuples_overlap(const crdt_tuples *t, size_t n, const void *p, size_t bytes) {
-    return dig_overlap(t->key, n * 8, p, bytes) || dig_overlap(t->ts, n * 8, p, bytes) ||
-           dig_overlap(t->rep, n * 4, p, bytes) || dig_overlap(t->tomb, n, p, bytes);
-}
 // the checks the digest and the selection share: mode, t, n_max, splitters
 static int dig_check_in(int mode, const crdt_tuples *t, size_t n_max, const uint64_t *sp, size_t m) {
     if (!t || (mode != CRDT_SET_LWW && mode != CRDT_SET_ORSET)) return CRDT_E_INVAL;
     if (n_max >= (1ULL << 62) || m >= kDigMaxSplit) return CRDT_E_RANGE;
     if ((m && !sp) || ((uintptr_t)sp & 7)) return CRDT_E_INVAL;
-    if (n_max && (!t->key || !t->ts || !t->rep || !t->tomb)) return CRDT_E_INVAL;
-    if (dig_misaligned(t)) return CRDT_E_INVAL;
+    if (n_max && tuples_null(t)) return CRDT_E_INVAL;
+    if (tuples_misaligned(t)) return CRDT_E_INVAL;
     if ((n_max + GT - 1) / GT >= 0x7fffffffULL) return CRDT_E_RANGE;
     return CRDT_OK;
 }
@@ -513,10 +369,10 @@ extern "C" int crdt_set_digest(crdt_ctx *ctx, int mode, const crdt_tuples *t, si
     if ((((uintptr_t)hash_out_dev | (uintptr_t)count_out_dev | (uintptr_t)n_dev) & 7) != 0) return CRDT_E_INVAL;
     const size_t ob = (m + 1) * 8;
     uint64_t *const outs[2] = {hash_out_dev, count_out_dev};
-    if (dig_overlap(hash_out_dev, ob, count_out_dev, ob)) return CRDT_E_INVAL;
+    if (spans_overlap(hash_out_dev, ob, count_out_dev, ob)) return CRDT_E_INVAL;
     for (int a = 0; a < 2; ++a) {
-        if (dig_tuples_overlap(t, n_max, outs[a], ob) || dig_overlap(splitters_dev, m * 8, outs[a], ob) ||
-            dig_overlap(n_dev, 8, outs[a], ob))
+        if (tuples_overlap(t, n_max, outs[a], ob) || spans_overlap(splitters_dev, m * 8, outs[a], ob) ||
+            spans_overlap(n_dev, 8, outs[a], ob))
             return CRDT_E_INVAL;
     }
     const hipStream_t s = ctx->stream;
@@ -546,10 +402,10 @@ extern "C" int crdt_set_digest_diff(crdt_ctx *ctx, const uint64_t *hash_a_dev, c
         return CRDT_E_INVAL;
     const void *in[4] = {hash_a_dev, count_a_dev, hash_b_dev, count_b_dev};
     for (int a = 0; a < 4; ++a) {
-        if (dig_overlap(in[a], n_buckets * 8, flags_out_dev, n_buckets) || dig_overlap(in[a], n_buckets * 8, n_diff_dev, 8))
+        if (spans_overlap(in[a], n_buckets * 8, flags_out_dev, n_buckets) || spans_overlap(in[a], n_buckets * 8, n_diff_dev, 8))
             return CRDT_E_INVAL;
     }
-    if (dig_overlap(flags_out_dev, n_buckets, n_diff_dev, 8)) return CRDT_E_INVAL;
+    if (spans_overlap(flags_out_dev, n_buckets, n_diff_dev, 8)) return CRDT_E_INVAL;
     const hipStream_t s = ctx->stream;
     k_dig_zero<<<1, 64, 0, s>>>(n_diff_dev);
     if (n_buckets)
@@ -567,51 +423,35 @@ extern "C" int crdt_set_select(crdt_ctx *ctx, int mode, const crdt_tuples *t, si
     rc = dig_check_in(mode, t, n_max, splitters_dev, m);
     if (rc) return rc;
     if (!out && src_out_dev) return CRDT_E_INVAL;
-    if ((out && dig_misaligned(out)) || (((uintptr_t)src_out_dev | (uintptr_t)count_dev | (uintptr_t)n_dev) & 7) != 0)
+    if ((out && tuples_misaligned(out)) || (((uintptr_t)src_out_dev | (uintptr_t)count_dev | (uintptr_t)n_dev) & 7) != 0)
         return CRDT_E_INVAL;
     if (out && n_max) {
-        if (!out->key || !out->ts || !out->rep || !out->tomb) return CRDT_E_INVAL;
-        const void *of[4] = {out->key, out->ts, out->rep, out->tomb};
-        const size_t ow[4] = {8, 8, 4, 1};
-        for (int a = 0; a < 4; ++a) {
-            const size_t by = n_max * ow[a];
-            if (dig_tuples_overlap(t, n_max, of[a], by) || dig_overlap(splitters_dev, m * 8, of[a], by) ||
-                dig_overlap(flags_dev, m + 1, of[a], by) || dig_overlap(src_out_dev, n_max * 8, of[a], by) ||
-                dig_overlap(count_dev, 8, of[a], by))
+        if (tuples_null(out)) return CRDT_E_INVAL;
+        const void *o[5] = {out->key, out->ts, out->rep, out->tomb, src_out_dev};   // (src_out_dev: null meets nothing)
+        const size_t ob[5] = {n_max * 8, n_max * 8, n_max * 4, n_max, n_max * 8};
+        for (int a = 0; a < 5; ++a) {
+            if (tuples_overlap(t, n_max, o[a], ob[a]) || spans_overlap(splitters_dev, m * 8, o[a], ob[a]) ||
+                spans_overlap(flags_dev, m + 1, o[a], ob[a]) || spans_overlap(count_dev, 8, o[a], ob[a]) ||
+                (a < 4 && spans_overlap(src_out_dev, n_max * 8, o[a], ob[a])))
                 return CRDT_E_INVAL;
         }
-        if (src_out_dev && (dig_tuples_overlap(t, n_max, src_out_dev, n_max * 8) ||
-                            dig_overlap(splitters_dev, m * 8, src_out_dev, n_max * 8) ||
-                            dig_overlap(flags_dev, m + 1, src_out_dev, n_max * 8) ||
-                            dig_overlap(count_dev, 8, src_out_dev, n_max * 8)))
-            return CRDT_E_INVAL;
     }
     const size_t ntiles = (n_max + GT - 1) / GT;
-    const size_t need = Carve::round((ntiles + 1) * 4) + Carve::round((ntiles + 1) * 8) +
-                        Carve::round((ntiles * 2 * GNW + 1) * 8) + 1024;
-    rc = ws_reserve(ctx, need);
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, false, false, 2 * GNW);
     if (rc) return rc;
-    Carve w(ctx->ws);
-    uint32_t *tcnt = w.take<uint32_t>(ntiles + 1);
-    uint64_t *ic = w.take<uint64_t>(ntiles + 1);
-    uint64_t *bits = w.take<uint64_t>(ntiles * 2 * GNW + 1);
     const bool lww = mode == CRDT_SET_LWW, wr = out != nullptr;
     const uint32_t mm = (uint32_t)m;
     const hipStream_t s = ctx->stream;
     const unsigned g = (unsigned)ntiles;
     if (ntiles) {
-        if (lww && wr) k_sel_count<true, true><<<g, GB, 0, s>>>(*t, n_max, n_dev, splitters_dev, mm, flags_dev, tcnt, bits);
-        else if (lww) k_sel_count<true, false><<<g, GB, 0, s>>>(*t, n_max, n_dev, splitters_dev, mm, flags_dev, tcnt, bits);
-        else if (wr) k_sel_count<false, true><<<g, GB, 0, s>>>(*t, n_max, n_dev, splitters_dev, mm, flags_dev, tcnt, bits);
-        else k_sel_count<false, false><<<g, GB, 0, s>>>(*t, n_max, n_dev, splitters_dev, mm, flags_dev, tcnt, bits);
+        if (lww && wr) k_sel_count<true, true><<<g, GB, 0, s>>>(*t, n_max, n_dev, splitters_dev, mm, flags_dev, w.tcnt, w.bits);
+        else if (lww) k_sel_count<true, false><<<g, GB, 0, s>>>(*t, n_max, n_dev, splitters_dev, mm, flags_dev, w.tcnt, w.bits);
+        else if (wr) k_sel_count<false, true><<<g, GB, 0, s>>>(*t, n_max, n_dev, splitters_dev, mm, flags_dev, w.tcnt, w.bits);
+        else k_sel_count<false, false><<<g, GB, 0, s>>>(*t, n_max, n_dev, splitters_dev, mm, flags_dev, w.tcnt, w.bits);
     }
-    k_sel_scan<<<1, 1024, 0, s>>>(n_max, n_dev, tcnt, wr ? ic : nullptr, count_dev, ctx->dev_status);
-    if (ntiles && wr) {
-        const bool sr = src_out_dev != nullptr;
-        if (lww && sr) k_sel_write<true, true><<<g, GB, 0, s>>>(*t, n_max, n_dev, bits, ic, *out, src_out_dev, ctx->dev_status);
-        else if (lww) k_sel_write<true, false><<<g, GB, 0, s>>>(*t, n_max, n_dev, bits, ic, *out, src_out_dev, ctx->dev_status);
-        else if (sr) k_sel_write<false, true><<<g, GB, 0, s>>>(*t, n_max, n_dev, bits, ic, *out, src_out_dev, ctx->dev_status);
-        else k_sel_write<false, false><<<g, GB, 0, s>>>(*t, n_max, n_dev, bits, ic, *out, src_out_dev, ctx->dev_status);
-    }
+    w.scan<NoCarry<>>(ctx, n_max, n_dev, 0, nullptr, wr, count_dev);   // (the count pass settled every bit)
+    if (ntiles && wr)
+        tile_write(lww, src_out_dev != nullptr, g, s, *t, n_max, n_dev, w.bits, w.ic, *out, src_out_dev, ctx->dev_status);
     return check_launch(ctx);
 }

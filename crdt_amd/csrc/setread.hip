@@ -18,16 +18,16 @@
 //           key's run), the tile's member count and, OR-Set only, a carry
 //           record.  No tile waits for another: each evaluates with an empty
 //           carry; what a carry can change is one bit, the first key end.
-//   scan  : one workgroup.  A tile's record is the FUNCTION it applies to
-//           the carry state (tomb-OR of the open tag run, live-any of the
-//           open key run: 2 bits, so a 4-entry table) plus the 4 outcomes of
-//           its first key end; composing tables is associative, so the
-//           carries into all tiles are a prefix scan of compositions --
-//           linear however many tiles one key or tag spans.  It patches the
-//           at most one affected emit bit and count per tile, scans the
-//           counts to offsets and stores the total.
-//   write : (elements only) reads the keys and the bitmap, stores each
-//           emitting key at its rank.
+//   scan  : k_tile_scan<ReadCarry> (settile.hpp; LWW: <NoCarry>).  A tile's
+//           record is the FUNCTION it applies to the carry state (tomb-OR of
+//           the open tag run, live-any of the open key run: 2 bits, so a
+//           4-entry table) plus the 4 outcomes of its first key end;
+//           composing tables is associative, so the carries into all tiles
+//           are a prefix scan of compositions -- linear however many tiles
+//           one key or tag spans.  The scan patches the at most one affected
+//           emit bit and count per tile.
+//   write : (elements only) k_tile_write_field (settile.hpp): each emitting
+//           key at its rank.
 // LWW needs no carry: the last tuple of a key's run holds the key's maximal
 // tag, and the walk back over equal-tag copies to the first one's tomb goes
 // through global memory, as k_lww_write's does.
@@ -36,15 +36,11 @@
 // tiles at or past min(*n_dev, n_max) do nothing, and *n_dev > n_max touches
 // no tuple, stores a count of ~0 and raises CRDT_DEV_RANGE.  No kernel reads
 // an index at or past that length or before 0.
-#include "scan.hpp"
+#include "settile.hpp"
 
 namespace crdt {
 
-constexpr int RT = 2048;                 // tuples per tile
-constexpr int RB = 256;                  // threads per tile (4 waves)
-constexpr int RWW = RT / RB;             // 64-tuple mask words per wave (consecutive: 512 tuples)
-constexpr int RNW = RT / 64;             // emit bitmap words per tile
-constexpr uint32_t kReadScanMax = 16384; // tiles per scan round (16 per thread)
+constexpr int RT = kTile, RB = kTileB, RWW = kTileWW, RNW = kTileNW;   // tile, its threads, words per wave and tile
 
 // ---- carry records.  State s = tor | live << 1 (tor: a tombstone seen in
 // the open tag run; live: a live tag closed in the open key run).  A record:
@@ -119,11 +115,20 @@ __device__ __forceinline__ uint32_t or_word_rec(uint64_t V, uint64_t ST, uint64_
     return r;
 }
 
-// the call's tuple count: n_max, or the device count when it is in range
-__device__ __forceinline__ bool read_len(uint64_t n_max, const uint64_t *__restrict__ n_dev, uint64_t *n) {
-    *n = n_dev ? *n_dev : n_max;
-    return *n <= n_max;
-}
+// the scan's view of a record: F composes, the first key end flips where its outcome differs from the empty carry's
+struct ReadCarry : PlainTiles {
+    static constexpr bool kHas = true;
+    static constexpr uint32_t kId = kRecId, kStride = RNW, kEmit = 0, kAux = 0;   // (`emit` alone)
+    static __device__ __forceinline__ uint32_t part(uint32_t r) { return r & 0xffu; }
+    static __device__ __forceinline__ uint32_t then(uint32_t a, uint32_t b) { return fn_then(a, b); }
+    static __device__ __forceinline__ uint32_t seed(uint32_t) { return kRecId; }
+    static __device__ __forceinline__ uint32_t enter(uint32_t p, uint32_t s) { return rec_f(p, s); }
+    static __device__ __forceinline__ uint32_t step(uint32_t s, uint32_t r) { return rec_f(r, s); }
+    static __device__ __forceinline__ uint32_t redecide(uint32_t r, uint32_t s) {
+        if (!((r & kRecKE) && rec_e(r, s) != rec_e(r, 0))) return 0;
+        return redo(rec_pos(r), true, false, rec_e(r, s) != 0);
+    }
+};
 
 // ---------------------------------------------------------------- OR-Set count pass
 template <bool BITS>
@@ -132,7 +137,7 @@ __global__ __launch_bounds__(RB) void k_or_read(crdt_tuples T, uint64_t n_max, c
                                                 uint64_t *__restrict__ bits) {
     __shared__ uint32_t s_rec[RB / 64], s_cnt[RB / 64];
     uint64_t n;
-    if (!read_len(n_max, n_dev, &n)) return;
+    if (!tile_len(n_max, n_dev, &n)) return;
     const uint64_t t = blockIdx.x, tb = t * RT;
     if (tb >= n) return;                                 // (uniform; so n > 0 below)
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -209,7 +214,7 @@ __global__ __launch_bounds__(RB) void k_lww_read(crdt_tuples T, uint64_t n_max, 
                                                  uint32_t *__restrict__ tcnt, uint64_t *__restrict__ bits) {
     __shared__ uint32_t s_cnt[RB / 64];
     uint64_t n;
-    if (!read_len(n_max, n_dev, &n)) return;
+    if (!tile_len(n_max, n_dev, &n)) return;
     const uint64_t t = blockIdx.x, tb = t * RT;
     if (tb >= n) return;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -255,141 +260,6 @@ __global__ __launch_bounds__(RB) void k_lww_read(crdt_tuples T, uint64_t n_max, 
     }
 }
 
-// ---------------------------------------------------------------- carry + scan
-// One workgroup, rounds of up to kReadScanMax tiles (k_chunk_scan's scheme,
-// a contiguous run of 16 tiles per thread): with rec, the carries into every
-// tile as a scan of the records' functions, the first key end of each tile
-// re-decided under its carry (emit bit in bits, when given, and the count);
-// then the counts to offsets (ic, when given; ic[tiles] = the total) and the
-// total to *count.
-__global__ __launch_bounds__(1024) void k_read_scan(uint64_t n_max, const uint64_t *__restrict__ n_dev,
-                                                    uint32_t *__restrict__ tcnt, const uint32_t *__restrict__ rec,
-                                                    uint64_t *__restrict__ bits, uint64_t *__restrict__ ic,
-                                                    uint64_t *__restrict__ count, uint32_t *__restrict__ err) {
-    constexpr int K = kReadScanMax / 1024;
-    __shared__ uint32_t s_f[16];
-    __shared__ uint64_t s_c[16];
-    uint64_t n;
-    if (!read_len(n_max, n_dev, &n)) {
-        if (threadIdx.x == 0) {
-            *count = ~0ull;
-            atomicOr(err, CRDT_DEV_RANGE);
-        }
-        return;
-    }
-    const uint64_t nt = (n + RT - 1) / RT;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t state = 0;                                  // the carry into the round's first tile
-    uint64_t base = 0;
-    for (uint64_t c0 = 0; c0 < nt; c0 += kReadScanMax) {
-        const uint64_t b = c0 + (uint64_t)threadIdx.x * K;
-        uint32_t v[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) v[q] = b + q < nt ? tcnt[b + q] : 0u;
-        if (rec) {
-            uint32_t rr[K], f = kRecId;
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                rr[q] = b + q < nt ? rec[b + q] : kRecId;
-                f = fn_then(f, rr[q] & 0xffu);
-            }
-            uint32_t x = f;                              // inclusive scan over the wave's threads
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = __shfl_up(x, o, 64);
-                if (lane >= o) x = fn_then(y, x);
-            }
-            if (lane == 63) s_f[w] = x;
-            uint32_t ex = __shfl_up(x, 1, 64);
-            if (lane == 0) ex = kRecId;
-            __syncthreads();
-            uint32_t pre = kRecId, tot = kRecId;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if (q < w) pre = fn_then(pre, s_f[q]);
-                tot = fn_then(tot, s_f[q]);
-            }
-            uint32_t s = rec_f(fn_then(pre, ex), state);
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                if (b + q < nt && (rr[q] & kRecKE) && rec_e(rr[q], s) != rec_e(rr[q], 0)) {
-                    const uint32_t p = rec_pos(rr[q]);
-                    if (bits) bits[(b + q) * RNW + (p >> 6)] ^= 1ull << (p & 63);
-                    v[q] += rec_e(rr[q], s) ? 1u : 0xffffffffu;
-                }
-                s = rec_f(rr[q], s);
-            }
-            state = rec_f(tot, state);
-        }
-        uint64_t sum = 0;
-#pragma unroll
-        for (int q = 0; q < K; ++q) sum += v[q];
-        uint64_t x = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_c[w] = x;
-        __syncthreads();
-        uint64_t run = base + x - sum, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            run += q < w ? s_c[q] : 0;
-            tot += s_c[q];
-        }
-        if (ic) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-                if (b + q < nt) ic[b + q] = run;
-                run += v[q];
-            }
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (ic) ic[nt] = base;
-        *count = base;
-    }
-}
-
-// ---------------------------------------------------------------- write pass
-__global__ __launch_bounds__(RB) void k_read_write(const uint64_t *__restrict__ key, uint64_t n_max,
-                                                   const uint64_t *__restrict__ n_dev,
-                                                   const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
-                                                   uint64_t *__restrict__ out, uint32_t *__restrict__ err) {
-    uint64_t n;
-    if (!read_len(n_max, n_dev, &n)) return;
-    const uint64_t t = blockIdx.x, tb = t * RT;
-    if (tb >= n) return;
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t wd = lane < RNW ? bits[t * RNW + lane] : 0ull;   // every wave holds the tile's words
-    const uint32_t pc = (uint32_t)__popcll(wd);
-    uint32_t x = pc;
-#pragma unroll
-    for (int o = 1; o < RNW; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    const uint32_t ex = x - pc;
-    const uint64_t base = ic[t];
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < RWW; ++j) {
-        const int q = wv * RWW + j;
-        const uint64_t wq = (uint64_t)__shfl((unsigned long long)wd, q, 64);
-        const uint32_t pq = __shfl(ex, q, 64);
-        if ((wq >> lane) & 1) {
-            const uint64_t i = tb + (uint64_t)q * 64 + lane;
-            const uint64_t at = base + pq + (uint32_t)__popcll(wq & ((1ull << lane) - 1));
-            if (i < n && at < n_max) out[at] = key[i];   // (a bitmap of this call's count pass never fails this)
-            else bad = true;
-        }
-    }
-    if (bad) atomicOr(err, CRDT_DEV_RANGE);
-}
-
 // ---------------------------------------------------------------- membership
 // out[i] = probes[i] occurs in v[0 .. n): one probe per lane, the binary
 // search of crdt_u64_lower_bound and an equality test.  (Its loads are what
@@ -400,7 +270,7 @@ __global__ void k_u64_contains(const uint64_t *__restrict__ v, uint64_t n_max, c
                                const uint64_t *__restrict__ probes, uint64_t m, uint8_t *__restrict__ out,
                                uint32_t *__restrict__ err) {
     uint64_t n;
-    if (!read_len(n_max, n_dev, &n)) {
+    if (!tile_len(n_max, n_dev, &n)) {
         n = 0;
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, CRDT_DEV_RANGE);
     }
@@ -416,11 +286,6 @@ __global__ void k_u64_contains(const uint64_t *__restrict__ v, uint64_t n_max, c
     }
 }
 
-static bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return an && bn && x < y + bn && y < x + an;
-}
-
 }  // namespace crdt
 
 using namespace crdt;
@@ -432,25 +297,16 @@ extern "C" int crdt_set_elements(crdt_ctx *ctx, int mode, const crdt_tuples *t, 
     if (!t || !count || (mode != CRDT_SET_LWW && mode != CRDT_SET_ORSET)) return CRDT_E_INVAL;
     if (n_max >= (1ULL << 62)) return CRDT_E_RANGE;
     if (n_max) {
-        if (!t->key || !t->ts || !t->rep || !t->tomb) return CRDT_E_INVAL;
-        if ((((uintptr_t)t->key | (uintptr_t)t->ts) & 7) | ((uintptr_t)t->rep & 3)) return CRDT_E_INVAL;
-        if (keys_out && (((uintptr_t)keys_out & 7) || ranges_overlap(keys_out, n_max * 8, t->key, n_max * 8) ||
-                         ranges_overlap(keys_out, n_max * 8, t->ts, n_max * 8) ||
-                         ranges_overlap(keys_out, n_max * 8, t->rep, n_max * 4) ||
-                         ranges_overlap(keys_out, n_max * 8, t->tomb, n_max)))
-            return CRDT_E_INVAL;
+        if (tuples_null(t) || tuples_misaligned(t)) return CRDT_E_INVAL;
+        if (keys_out && (((uintptr_t)keys_out & 7) || tuples_overlap(t, n_max, keys_out, n_max * 8))) return CRDT_E_INVAL;
     }
     const size_t ntiles = (n_max + RT - 1) / RT;
     if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;
-    const size_t need = Carve::round((ntiles + 1) * 4) + Carve::round((ntiles + 1) * 4) +
-                        Carve::round((ntiles + 1) * 8) + Carve::round((ntiles * RNW + 1) * 8) + 1024;
-    rc = ws_reserve(ctx, need);
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, false, true, RNW);
     if (rc) return rc;
-    Carve w(ctx->ws);
-    uint32_t *tcnt = w.take<uint32_t>(ntiles + 1);
-    uint32_t *rec = w.take<uint32_t>(ntiles + 1);
-    uint64_t *ic = w.take<uint64_t>(ntiles + 1);
-    uint64_t *bits = w.take<uint64_t>(ntiles * RNW + 1);
+    uint32_t *const tcnt = w.tcnt, *const rec = w.rec;
+    uint64_t *const ic = w.ic, *const bits = w.bits;
     const bool lww = mode == CRDT_SET_LWW, wr = keys_out != nullptr;
     const hipStream_t s = ctx->stream;
     if (ntiles) {
@@ -460,10 +316,11 @@ extern "C" int crdt_set_elements(crdt_ctx *ctx, int mode, const crdt_tuples *t, 
         else if (wr) k_or_read<true><<<g, RB, 0, s>>>(*t, n_max, n_dev, tcnt, rec, bits);
         else k_or_read<false><<<g, RB, 0, s>>>(*t, n_max, n_dev, tcnt, rec, bits);
     }
-    k_read_scan<<<1, 1024, 0, s>>>(n_max, n_dev, tcnt, lww ? nullptr : rec, wr ? bits : nullptr, wr ? ic : nullptr,
-                                   count, ctx->dev_status);
+    if (lww) w.scan<NoCarry<>>(ctx, n_max, n_dev, 0, nullptr, wr, count);
+    else w.scan<ReadCarry>(ctx, n_max, n_dev, 0, nullptr, wr, count);
     if (ntiles && wr)
-        k_read_write<<<(unsigned)ntiles, RB, 0, s>>>(t->key, n_max, n_dev, bits, ic, keys_out, ctx->dev_status);
+        k_tile_write_field<uint64_t><<<(unsigned)ntiles, RB, 0, s>>>(t->key, n_max, n_dev, bits, ic, keys_out,
+                                                                     ctx->dev_status);
     return check_launch(ctx);
 }
 
