@@ -52,6 +52,19 @@
 // tuple, stores a count of ~0 and raises CRDT_DEV_RANGE; no kernel reads an
 // index at or past min(*n_dev, n_max) of its side, or before 0, nor a context
 // at or past its n_ctx.
+//
+// The ranged form (crdt_orset_merge_causal_ranges) merges a
+// whole state a with what a peer shipped for the buckets of crdt_set_digest
+// whose digests differ.  The merge is not monotone -- a tag a holds and b's
+// context covers is dropped unless b's copy is in the operand -- so in an
+// unflagged bucket, where equal digests say both replicas hold the same
+// canonical tuples, "present in both" is "present in a": the tag survives iff
+// a holds it present, b's copies there are ignored and no context is read.
+// One predicate of the count pass (k_causal_count<*, true>); a tag lies in one
+// bucket, so every tile masks its copies alike and the scan, the write pass
+// and the split run unchanged: a run that ends on an ignored b copy loads the
+// same tag there, `srca` is set, and the source walk goes to a's first copy.
+// No kernel reads a splitter at or past m or a flag at or past m + 1.
 #include "settile.hpp"
 
 namespace crdt {
@@ -62,6 +75,7 @@ constexpr int UNI = UT / UCB;              // merge items per count thread
 constexpr int UNW = kTileNW;               // words per tile and bitmap
 constexpr int UWB = 256;                   // write pass threads (one output each per round)
 constexpr int UCAP = UT + 4;               // staged slots: each side's run, the element before and the one after it
+constexpr size_t kCausalMaxSplit = (size_t)1 << 24;   // (crdt_set_digest's bound on m)
 
 // ---- the open tag run's state and a segment's record
 constexpr uint32_t kUHasA = 1, kUTorA = 2, kUHasB = 4, kUTorB = 8;   // a / b: copy seen, tomb-OR
@@ -121,14 +135,56 @@ __global__ __launch_bounds__(256) void k_causal_ctx(const uint64_t *__restrict__
     out[c] = x > y ? x : y;
 }
 
+// lo + #{ j in [lo, hi) : sp[j] <= key } for ascending sp (setdigest.hip's
+// dig_ub): always a value in [lo, max(lo, hi)], and only sp[lo .. hi) is read
+__device__ __forceinline__ uint32_t cz_ub(const uint64_t *__restrict__ sp, uint32_t lo, uint32_t hi, uint64_t key) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (sp[mid] <= key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The same count over sp[0 .. m) for a wave-uniform key by a whole wave (every
+// lane active): 64 probes a round, so 255 splitters take two dependent loads
+// where the binary search takes eight.  Reads sp[lo .. hi) only and returns a
+// value in [0, m], whatever sp holds.
+__device__ __forceinline__ uint32_t cz_ub_wave(const uint64_t *__restrict__ sp, uint32_t m, uint64_t key, uint32_t lane) {
+    uint32_t lo = 0, hi = m;
+    while (lo < hi) {                                    // (uniform)
+        const uint32_t span = hi - lo;
+        if (span <= 64) {
+            const bool p = lane < span && sp[lo + lane] <= key;
+            return lo + (uint32_t)__popcll(__ballot(p));
+        }
+        // probe c_l = lo + floor(l span / 64), ascending from lo: the first cnt hold (ascending sp)
+        const uint32_t c = lo + (uint32_t)(((uint64_t)lane * span) >> 6);
+        const uint32_t cnt = (uint32_t)__popcll(__ballot(sp[c] <= key));
+        const uint32_t nlo = cnt ? lo + (uint32_t)(((uint64_t)(cnt - 1) * span) >> 6) + 1 : lo;
+        hi = cnt < 64 ? lo + (uint32_t)(((uint64_t)cnt * span) >> 6) : hi;
+        lo = nlo;
+    }
+    return lo;
+}
+
 // ---------------------------------------------------------------- count
-template <bool BITS>
+// RANGED (crdt_orset_merge_causal_ranges): sp[0 .. m) and flags[0 .. m] are
+// crdt_set_digest's buckets.  In an unflagged bucket b is taken to hold what a
+// holds: a b item keeps its `isb` bit and adds nothing to the run state, a run
+// end decides by a's bits alone (covered by b: false) and reads no context.
+// Every wave searches the splitters for its tile's first and last key (uniform,
+// 64 probes a round); one bucket, the common case, is one flag load, else an
+// item searches between the two.  Every search is an upper bound inside [0, m].
+template <bool BITS, bool RANGED>
 __global__ __launch_bounds__(UCB) void k_causal_count(crdt_tuples A, uint64_t na_max, const uint64_t *__restrict__ na_dev,
                                                       const uint64_t *__restrict__ ca, uint32_t nca, crdt_tuples B,
                                                       uint64_t nb_max, const uint64_t *__restrict__ nb_dev,
                                                       const uint64_t *__restrict__ cb, uint32_t ncb,
                                                       const uint64_t *__restrict__ split, uint32_t *__restrict__ tcnt,
-                                                      uint32_t *__restrict__ rec, uint64_t *__restrict__ bits) {
+                                                      uint32_t *__restrict__ rec, uint64_t *__restrict__ bits,
+                                                      const uint64_t *__restrict__ sp, uint32_t m,
+                                                      const uint8_t *__restrict__ flags) {
     // staged: a slots 0 .. ta + 1 = A[i0 - 1 .. i1], then b slots = B[j0 - 1 .. j1]
     __shared__ uint64_t sk[UCAP];
     __shared__ uint64_t st[UCAP];
@@ -187,11 +243,22 @@ __global__ __launch_bounds__(UCB) void k_causal_count(crdt_tuples A, uint64_t na
     auto same = [&](uint32_t x, uint32_t y) -> bool {   // slots x, y carry one tag
         return sk[x] == sk[y] && st[x] == st[y] && sr[x] == sr[y];
     };
+    // RANGED: the tile's bucket span [blo, bhi] from its first and last key; one bucket: its flag
+    uint32_t blo = 0, bhi = 0;
+    bool one = true, f1 = true;
+    if constexpr (RANGED) {
+        const uint64_t fa = sk[1], la = sk[ta], fb = sk[so + 1], lb = sk[so + tb];   // (a side with no item in the tile is not taken)
+        const uint64_t kf = ta && (!tb || fa < fb) ? fa : fb, kl = ta && (!tb || la > lb) ? la : lb;
+        blo = __builtin_amdgcn_readfirstlane(cz_ub_wave(sp, m, kf, threadIdx.x & 63));
+        bhi = __builtin_amdgcn_readfirstlane(cz_ub_wave(sp, m, kl, threadIdx.x & 63));
+        one = blo == bhi;
+        f1 = one && flags[blo] != 0;
+    }
     const uint32_t k0 = threadIdx.x * UNI < tn ? threadIdx.x * UNI : tn;
     const uint32_t k1 = k0 + UNI < tn ? k0 + UNI : tn;
     uint32_t isb = 0, emit = 0, sa = 0;
     uint32_t state = 0, lead = 0, first = 0, fslot = 0;  // open run's state; the first run end's state, item and slot
-    bool seen = false;
+    bool seen = false, ffl = true;                       // RANGED: the first run end's bucket is flagged
     if (k0 < k1) {
         uint32_t lo = k0 > tb ? k0 - tb : 0, hi = k0 < ta ? k0 : ta;
         while (lo < hi) {
@@ -210,15 +277,21 @@ __global__ __launch_bounds__(UCB) void k_causal_count(crdt_tuples A, uint64_t na
             take_a = ha && (!hb || le(ia, ib));
             const bool end = !((ha || hb) && same(cur, take_a ? 1 + ia : so + 1 + ib));
             if (!is_a) isb |= 1u << i;
-            state |= is_a ? (kUHasA | (sm[cur] ? kUTorA : 0u)) : (kUHasB | (sm[cur] ? kUTorB : 0u));
+            bool fl = true;                              // RANGED: the item's bucket is flagged (wanted at a b item and a run end)
+            if constexpr (RANGED) {
+                fl = f1;
+                if (!one && (!is_a || end)) fl = flags[cz_ub(sp, blo, bhi, sk[cur])] != 0;
+            }
+            state |= is_a ? (kUHasA | (sm[cur] ? kUTorA : 0u)) : (fl ? (kUHasB | (sm[cur] ? kUTorB : 0u)) : 0u);
             if (end) {
                 if (!seen) {
                     seen = true;
                     lead = state;
                     first = i;
                     fslot = cur;
+                    if constexpr (RANGED) ffl = fl;
                 } else {
-                    const uint32_t d = cz_decide(state, st[cur], sr[cur], ca, nca, cb, ncb);
+                    const uint32_t d = fl ? cz_decide(state, st[cur], sr[cur], ca, nca, cb, ncb) : (cz_pa(state) ? 3u : 0u);
                     if (d & 1) emit |= 1u << i;
                     if (d & 2) sa |= 1u << i;
                 }
@@ -248,13 +321,14 @@ __global__ __launch_bounds__(UCB) void k_causal_count(crdt_tuples A, uint64_t na
             const uint64_t fts = st[fslot];
             const uint32_t frep = sr[fslot];
             if (!(pre & kUEnd)) {                        // the tile's first run end: the scan re-decides it under the carry
-                const bool cva = cz_cov(ca, nca, frep, fts), cvb = cz_cov(cb, ncb, frep, fts);
+                // (an unflagged bucket: neither context is read, both bits 0 -- no b bit reaches the run's state)
+                const bool cva = ffl && cz_cov(ca, nca, frep, fts), cvb = ffl && cz_cov(cb, ncb, frep, fts);
                 const uint32_t d = cz_keep(all, cva, cvb);
                 if (d & 1) emit |= 1u << first;
                 if (d & 2) sa |= 1u << first;
                 s_first = (all << 5) | (cva ? 1u << 9 : 0u) | (cvb ? 1u << 10 : 0u) | ((k0 + first) << 16);
             } else {
-                const uint32_t d = cz_decide(all, fts, frep, ca, nca, cb, ncb);
+                const uint32_t d = ffl ? cz_decide(all, fts, frep, ca, nca, cb, ncb) : (cz_pa(all) ? 3u : 0u);
                 if (d & 1) emit |= 1u << first;
                 if (d & 2) sa |= 1u << first;
             }
@@ -389,15 +463,20 @@ static int causal_fields(const crdt_tuples *t, size_t n, CausalSpan *s) {
 
 using namespace crdt;
 
-extern "C" int crdt_orset_merge_causal(crdt_ctx *ctx, const crdt_tuples *a, size_t na_max, const uint64_t *na_dev,
-                                       const uint64_t *ctx_a_dev, size_t n_ctx_a, const crdt_tuples *b, size_t nb_max,
-                                       const uint64_t *nb_dev, const uint64_t *ctx_b_dev, size_t n_ctx_b,
-                                       const crdt_tuples *out, int64_t *src_out_dev, uint64_t *ctx_out_dev,
-                                       uint64_t *count) {
+// both entry points: ranged takes crdt_set_digest's buckets (sp, m, flags)
+static int causal_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na_max, const uint64_t *na_dev,
+                        const uint64_t *ctx_a_dev, size_t n_ctx_a, const crdt_tuples *b, size_t nb_max,
+                        const uint64_t *nb_dev, const uint64_t *ctx_b_dev, size_t n_ctx_b, bool ranged,
+                        const uint64_t *sp, size_t m, const uint8_t *flags, const crdt_tuples *out,
+                        int64_t *src_out_dev, uint64_t *ctx_out_dev, uint64_t *count) {
     int rc = bind(ctx);
     if (rc) return rc;
     if (!a || !b || !count) return CRDT_E_INVAL;
     if (na_max >= (1ULL << 62) || nb_max >= (1ULL << 62)) return CRDT_E_RANGE;
+    if (ranged) {
+        if (m >= kCausalMaxSplit) return CRDT_E_RANGE;
+        if (!flags || (m && !sp) || ((uintptr_t)sp & 7)) return CRDT_E_INVAL;
+    }
     if (n_ctx_a >= (1ULL << 32) || n_ctx_b >= (1ULL << 32)) return CRDT_E_RANGE;
     if ((n_ctx_a && !ctx_a_dev) || (n_ctx_b && !ctx_b_dev)) return CRDT_E_INVAL;
     if (!out && src_out_dev) return CRDT_E_INVAL;
@@ -412,13 +491,17 @@ extern "C" int crdt_orset_merge_causal(crdt_ctx *ctx, const crdt_tuples *a, size
     const size_t ntiles = (cap + UT - 1) / UT;
     if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;
     {
-        CausalSpan in[12], o[6];
+        CausalSpan in[14], o[6];
         int ni = causal_fields(a, na_max, in), no = 0;
         ni += causal_fields(b, nb_max, in + ni);
         in[ni++] = {ctx_a_dev, n_ctx_a * 8};
         in[ni++] = {ctx_b_dev, n_ctx_b * 8};
         in[ni++] = {na_dev, 8};
         in[ni++] = {nb_dev, 8};
+        if (ranged) {
+            in[ni++] = {sp, m * 8};
+            in[ni++] = {flags, m + 1};
+        }
         if (out) no = causal_fields(out, cap, o);
         o[no++] = {src_out_dev, cap * 8};
         o[no++] = {ctx_out_dev, n_ctx * 8};
@@ -441,12 +524,19 @@ extern "C" int crdt_orset_merge_causal(crdt_ctx *ctx, const crdt_tuples *a, size
         const unsigned g = (unsigned)ntiles;
         k_mp_split<UT, TupleLe<false>, PlainTiles><<<mp_split_grid(ntiles), 256, 0, s>>>(*a, na_max, na_dev, *b, nb_max,
                                                                                         nb_dev, w.split);
-        if (wr)
-            k_causal_count<true><<<g, UCB, 0, s>>>(*a, na_max, na_dev, ctx_a_dev, nca, *b, nb_max, nb_dev, ctx_b_dev, ncb,
-                                                   w.split, w.tcnt, w.rec, w.bits);
+        const uint32_t mm = (uint32_t)m;
+        if (ranged && wr)
+            k_causal_count<true, true><<<g, UCB, 0, s>>>(*a, na_max, na_dev, ctx_a_dev, nca, *b, nb_max, nb_dev, ctx_b_dev,
+                                                         ncb, w.split, w.tcnt, w.rec, w.bits, sp, mm, flags);
+        else if (ranged)
+            k_causal_count<false, true><<<g, UCB, 0, s>>>(*a, na_max, na_dev, ctx_a_dev, nca, *b, nb_max, nb_dev, ctx_b_dev,
+                                                          ncb, w.split, w.tcnt, w.rec, w.bits, sp, mm, flags);
+        else if (wr)
+            k_causal_count<true, false><<<g, UCB, 0, s>>>(*a, na_max, na_dev, ctx_a_dev, nca, *b, nb_max, nb_dev, ctx_b_dev,
+                                                          ncb, w.split, w.tcnt, w.rec, w.bits, nullptr, 0u, nullptr);
         else
-            k_causal_count<false><<<g, UCB, 0, s>>>(*a, na_max, na_dev, ctx_a_dev, nca, *b, nb_max, nb_dev, ctx_b_dev,
-                                                    ncb, w.split, w.tcnt, w.rec, w.bits);
+            k_causal_count<false, false><<<g, UCB, 0, s>>>(*a, na_max, na_dev, ctx_a_dev, nca, *b, nb_max, nb_dev, ctx_b_dev,
+                                                           ncb, w.split, w.tcnt, w.rec, w.bits, nullptr, 0u, nullptr);
     }
     w.scan<CausalCarry>(ctx, na_max, na_dev, nb_max, nb_dev, wr, count);
     if (ntiles && wr) {
@@ -458,4 +548,23 @@ extern "C" int crdt_orset_merge_causal(crdt_ctx *ctx, const crdt_tuples *a, size
                                                                    w.ic, *out, src_out_dev, ctx->dev_status);
     }
     return check_launch(ctx);
+}
+
+extern "C" int crdt_orset_merge_causal(crdt_ctx *ctx, const crdt_tuples *a, size_t na_max, const uint64_t *na_dev,
+                                       const uint64_t *ctx_a_dev, size_t n_ctx_a, const crdt_tuples *b, size_t nb_max,
+                                       const uint64_t *nb_dev, const uint64_t *ctx_b_dev, size_t n_ctx_b,
+                                       const crdt_tuples *out, int64_t *src_out_dev, uint64_t *ctx_out_dev,
+                                       uint64_t *count) {
+    return causal_merge(ctx, a, na_max, na_dev, ctx_a_dev, n_ctx_a, b, nb_max, nb_dev, ctx_b_dev, n_ctx_b, false, nullptr,
+                        0, nullptr, out, src_out_dev, ctx_out_dev, count);
+}
+
+extern "C" int crdt_orset_merge_causal_ranges(crdt_ctx *ctx, const crdt_tuples *a, size_t na_max, const uint64_t *na_dev,
+                                              const uint64_t *ctx_a_dev, size_t n_ctx_a, const crdt_tuples *b,
+                                              size_t nb_max, const uint64_t *nb_dev, const uint64_t *ctx_b_dev,
+                                              size_t n_ctx_b, const uint64_t *splitters_dev, size_t m,
+                                              const uint8_t *flags_dev, const crdt_tuples *out, int64_t *src_out_dev,
+                                              uint64_t *ctx_out_dev, uint64_t *count_dev) {
+    return causal_merge(ctx, a, na_max, na_dev, ctx_a_dev, n_ctx_a, b, nb_max, nb_dev, ctx_b_dev, n_ctx_b, true,
+                        splitters_dev, m, flags_dev, out, src_out_dev, ctx_out_dev, count_dev);
 }

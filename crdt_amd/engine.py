@@ -565,22 +565,30 @@ class Engine:
         a length is out of range.  ``n_a_dev`` / ``n_b_dev`` as in
         :meth:`set_delta`; with ``trim`` the device status is checked and the
         sliced results returned."""
+        out, src, ctx_out = self._causal_outputs("causal_merge", a, ctx_a, b, ctx_b, out, src, ctx_out, with_src)
+        count = self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out, count)
+        return self._causal_result(out, src, ctx_out, count, trim)
+
+    def _causal_outputs(self, who: str, a: TupleSet, ctx_a, b: TupleSet, ctx_b, out, src, ctx_out, with_src: bool):
+        """The output buffers of a causal merge, allocated where not given and checked where given."""
         n = len(a) + len(b)
         out = TupleSet.empty(max(n, 1), self.device) if out is None else out
         if len(out) < n:
-            raise ValueError("causal_merge: out holds fewer tuples than len(a) + len(b)")
+            raise ValueError(f"{who}: out holds fewer tuples than len(a) + len(b)")
         if src is None and with_src:
             src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
         if src is not None:
             self._check(src, itemsize=8)
             if src.dtype != torch.int64 or src.numel() < n:
-                raise ValueError("causal_merge: src must be int64 and hold len(a) + len(b) entries")
+                raise ValueError(f"{who}: src must be int64 and hold len(a) + len(b) entries")
         nc = max(0 if ctx_a is None else ctx_a.numel(), 0 if ctx_b is None else ctx_b.numel())
         ctx_out = torch.empty(nc, dtype=torch.int64, device=self.device) if ctx_out is None else ctx_out
         self._check(ctx_out, itemsize=8)
         if ctx_out.numel() < nc:
-            raise ValueError("causal_merge: ctx_out holds fewer entries than the longer context")
-        count = self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out, count)
+            raise ValueError(f"{who}: ctx_out holds fewer entries than the longer context")
+        return out, src, ctx_out
+
+    def _causal_result(self, out: TupleSet, src, ctx_out, count, trim: bool):
         if trim:
             self.check_device()
             k = int(count.item())
@@ -594,8 +602,9 @@ class Engine:
         synchronisation): nothing is written but the count."""
         return self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, None, None, None, count)
 
-    def _causal_merge(self, a: TupleSet, ctx_a, b: TupleSet, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out,
-                      count) -> torch.Tensor:
+    def _causal_merge(self, a: TupleSet, ctx_a, b: TupleSet, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out, count,
+                      ranges=None) -> torch.Tensor:
+        """crdt_orset_merge_causal, or with ranges = (splitters, flags) crdt_orset_merge_causal_ranges."""
         count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
         self._check(count, itemsize=8)
         for s in (a, b) + (() if out is None else (out,)):
@@ -605,12 +614,21 @@ class Engine:
         for x in (ctx_a, ctx_b, n_a_dev, n_b_dev):
             if x is not None:
                 self._check(x, itemsize=8)
+        fn, mid = "crdt_orset_merge_causal", ()
+        if ranges is not None:
+            splitters, flags = ranges
+            m = 0 if splitters is None else splitters.numel()
+            self._check(flags, itemsize=1)
+            if flags.numel() < m + 1:
+                raise ValueError("causal_merge_ranges: flags must hold len(splitters) + 1 entries")
+            if splitters is not None:
+                self._check(splitters, itemsize=8)
+            fn, mid = "crdt_orset_merge_causal_ranges", (_ptr(splitters) if m else None, m, _ptr(flags))
         ca, cb = a.c(), b.c()
         co = None if out is None else out.c()
-        self._call("crdt_orset_merge_causal", C.byref(ca), len(a), _ptr(n_a_dev), _ptr(ctx_a),
-                   0 if ctx_a is None else ctx_a.numel(), C.byref(cb), len(b), _ptr(n_b_dev), _ptr(ctx_b),
-                   0 if ctx_b is None else ctx_b.numel(), None if co is None else C.byref(co), _ptr(src),
-                   _ptr(ctx_out), count.data_ptr())
+        self._call(fn, C.byref(ca), len(a), _ptr(n_a_dev), _ptr(ctx_a), 0 if ctx_a is None else ctx_a.numel(),
+                   C.byref(cb), len(b), _ptr(n_b_dev), _ptr(ctx_b), 0 if ctx_b is None else ctx_b.numel(), *mid,
+                   None if co is None else C.byref(co), _ptr(src), _ptr(ctx_out), count.data_ptr())
         return count
 
     def causal_map_merge(self, a: TupleSet, a_val: torch.Tensor, ctx_a: torch.Tensor | None, b: TupleSet,
@@ -622,6 +640,60 @@ class Engine:
         if a_val.shape[0] != len(a) or b_val.shape[0] != len(b):
             raise ValueError("causal_map_merge: one value per tuple on each side")
         out, src, ctx_out, count = self.causal_merge(a, ctx_a, b, ctx_b, with_src=True)
+        return out, self.gather_src(src, a_val, b_val, n_dev=count), ctx_out, count
+
+    # -- the causal merge restricted to the key ranges whose digests differ
+    #    (crdt_orset_merge_causal_ranges)
+    def causal_merge_ranges(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet, ctx_b: torch.Tensor | None,
+                            splitters: torch.Tensor | None, flags: torch.Tensor,
+                            n_a_dev: torch.Tensor | None = None, n_b_dev: torch.Tensor | None = None,
+                            out: TupleSet | None = None, src: torch.Tensor | None = None,
+                            ctx_out: torch.Tensor | None = None, count: torch.Tensor | None = None,
+                            with_src: bool = False, trim: bool = False):
+        """:meth:`causal_merge` of the receiver's whole causal state ``a``
+        with what a peer shipped for the buckets whose digests differ: ``b``
+        is normally ``set_select(B, False, splitters, flags)`` with its device
+        count as ``n_b_dev``, ``ctx_b`` the peer's whole context.  The causal
+        merge is not monotone -- a tag a holds and ctx_b covers is dropped
+        unless b's copy is in the operand -- so the buckets come along
+        (:meth:`set_digest`'s: ``splitters``, None or empty for one bucket;
+        ``flags`` uint8[len(splitters) + 1], e.g. :meth:`digest_diff`'s).  In
+        a flagged bucket the rule of :meth:`causal_merge` applies unchanged;
+        in an unflagged one b is taken to hold what a holds: a tag survives
+        iff a holds it present, b's copies there are ignored entirely (never
+        emitted, never named by src, no revival of a tag tombstoned on a) and
+        neither context is read.  Every flag set equals :meth:`causal_merge`
+        bit for bit; no flag set gives a's present tags and the merged
+        context.  The caller vouches that the replicas' canonical tuples are
+        equal in every unflagged bucket.  Arguments and results otherwise as
+        :meth:`causal_merge`."""
+        out, src, ctx_out = self._causal_outputs("causal_merge_ranges", a, ctx_a, b, ctx_b, out, src, ctx_out, with_src)
+        count = self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out, count,
+                                   ranges=(splitters, flags))
+        return self._causal_result(out, src, ctx_out, count, trim)
+
+    def causal_merge_ranges_count(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet,
+                                  ctx_b: torch.Tensor | None, splitters: torch.Tensor | None, flags: torch.Tensor,
+                                  n_a_dev: torch.Tensor | None = None, n_b_dev: torch.Tensor | None = None,
+                                  count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(causal_merge_ranges(...)) alone (int64[1] on the device, no
+        synchronisation): nothing is written but the count."""
+        return self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, None, None, None, count,
+                                  ranges=(splitters, flags))
+
+    def causal_map_merge_ranges(self, a: TupleSet, a_val: torch.Tensor, ctx_a: torch.Tensor | None, b: TupleSet,
+                                b_val: torch.Tensor, ctx_b: torch.Tensor | None, splitters: torch.Tensor | None,
+                                flags: torch.Tensor, n_b_dev: torch.Tensor | None = None):
+        """:meth:`causal_merge_ranges` of states that keep a value beside each
+        tuple (a_val[i] belongs to a's tuple i; ``b``, ``b_val`` and
+        ``n_b_dev`` are :meth:`map_select`'s tuples, column and count):
+        returns (out, out_val, ctx_out, count), device-resident -- the merge,
+        then one :meth:`gather_src` chained off its device count, no
+        read-back."""
+        if a_val.shape[0] != len(a) or b_val.shape[0] != len(b):
+            raise ValueError("causal_map_merge_ranges: one value per tuple on each side")
+        out, src, ctx_out, count = self.causal_merge_ranges(a, ctx_a, b, ctx_b, splitters, flags, n_b_dev=n_b_dev,
+                                                            with_src=True)
         return out, self.gather_src(src, a_val, b_val, n_dev=count), ctx_out, count
 
     # -- range digests: where two states differ, without shipping either

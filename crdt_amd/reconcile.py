@@ -6,7 +6,9 @@ with the same splitters, digest their state per bucket
 (:meth:`Engine.set_digest`, 16 bytes a bucket), exchange the digests, flag the
 buckets that differ (:meth:`Engine.digest_diff`) and ship only those
 (:meth:`Engine.set_select`).  The reference's gossip pull ships the entire
-Diff every round (main.go:153-170, :245-256).
+Diff every round (main.go:153-170, :245-256).  :func:`causal_round` is the
+same round for the tombstone-free OR-Set, whose merge is not monotone and
+needs the buckets along (:meth:`Engine.causal_merge_ranges`).
 
 Everything here runs in the library's HIP kernels; torch allocates, indexes
 the splitter keys and fills buffers.
@@ -94,3 +96,45 @@ def reconcile_round(eng: Engine, A: TupleSet, B: TupleSet, lww: bool, splitters:
     ma, ca, ship_b = _ship_and_merge(eng, A, B, lww, splitters, flags)
     mb, cb, ship_a = _ship_and_merge(eng, B, A, lww, splitters, flags)
     return (ma, ca), (mb, cb), flags, (ship_a, ship_b)
+
+
+def causal_round(eng: Engine, A: TupleSet, ctx_a: torch.Tensor | None, B: TupleSet, ctx_b: torch.Tensor | None,
+                 splitters: torch.Tensor | None):
+    """One reconciliation round between the causal OR-Set states ``(A,
+    ctx_a)`` and ``(B, ctx_b)``, both on ``eng``'s device,
+    standing in for two replicas: each side's OR-Set-mode digest over
+    ``splitters``, the diff of the two, each side's selection of the flagged
+    buckets, and :meth:`Engine.causal_merge_ranges` of each whole state with
+    the other side's selection under the other side's whole context.  The
+    selection's device count goes straight in as the merge's ``n_b_dev``.
+    Everything is enqueued on the stream with no synchronisation and no
+    read-back.
+
+    The plain causal merge cannot take a selection: it is not monotone, and a
+    tag the receiver holds that the peer's context covers is dropped unless
+    the peer's copy is in the operand.  The ranged merge decides an unflagged
+    bucket by the receiver's state alone.
+
+    Returns ``((MA, ca, ctx), (MB, cb, ctx), flags, (ship_a, ship_b))``: the
+    merged states (TupleSets of capacity len(A) + len(B), their first ``ca``
+    / ``cb`` tuples valid, int64[1] device counts) each with its merged
+    context, the uint8 flags of the buckets that differed, and the numbers of
+    tuples A and B had to ship (int64[1] on the device).  MA and MB both equal
+    ``causal_merge(A, B)``, tuple for tuple, and both contexts its merged
+    context, with probability about 1 - 2^-64 per differing bucket.
+
+    What crosses the wire between real replicas is the digests (16 bytes a
+    bucket), the two contexts (8 bytes a replica) and the selections.
+    Recursion with finer splitters inside the flagged ranges works as for
+    :func:`reconcile_round`: unflagged coarse buckets stay unflagged under the
+    finer cut, so only the differing sub-ranges ship.
+    """
+    da = eng.set_digest(A, False, splitters)
+    db = eng.set_digest(B, False, splitters)
+    flags, _ = eng.digest_diff(da, db)
+    sel_a, ship_a = eng.set_select(A, False, splitters, flags)
+    sel_b, ship_b = eng.set_select(B, False, splitters, flags)
+    sel_a, sel_b = sel_a.slice(len(A)), sel_b.slice(len(B))      # (an empty state's buffer holds one slot)
+    ma, ctx_ma, ca = eng.causal_merge_ranges(A, ctx_a, sel_b, ctx_b, splitters, flags, n_b_dev=ship_b)
+    mb, ctx_mb, cb = eng.causal_merge_ranges(B, ctx_b, sel_a, ctx_a, splitters, flags, n_b_dev=ship_a)
+    return (ma, ca, ctx_ma), (mb, cb, ctx_mb), flags, (ship_a, ship_b)

@@ -287,6 +287,41 @@ func OrsetMergeCausalCount(a *C.crdt_tuples, naMax int, naDev, ctxADev *C.uint64
 	return OrsetMergeCausal(a, naMax, naDev, ctxADev, nCtxA, b, nbMax, nbDev, ctxBDev, nCtxB, nil, nil, nil, countDev)
 }
 
+// OrsetMergeCausalRanges: OrsetMergeCausal of the receiver's whole causal state
+// a with what a peer shipped for the key ranges whose digests differ -- b is
+// normally SetSelect(B, OR-Set, splittersDev, flagsDev), nbDev its countDev,
+// ctxBDev the peer's whole context.  The causal merge is not monotone (a tag a
+// holds and b's context covers is dropped unless b's copy is in the operand),
+// so the buckets come along: SetDigest's, bucket(key) = the number of splitters
+// <= key, m + 1 flags.  In a flagged bucket OrsetMergeCausal's rule applies
+// unchanged; in an unflagged one b is taken to hold what a holds -- a tag
+// survives iff a holds it present, b's copies there are ignored entirely and
+// neither context is read.  Every flag set equals OrsetMergeCausal(a, b) bit
+// for bit; no flag set gives a's present tags.  Not symmetric in a and b: run
+// it in both directions and both replicas hold merge(A, B).  The caller
+// vouches that the replicas' canonical tuples are equal in every unflagged
+// bucket (what equal digests say).  Everything else as OrsetMergeCausal.
+// Enqueued: crdt_ctx_sync before reading.
+func OrsetMergeCausalRanges(a *C.crdt_tuples, naMax int, naDev, ctxADev *C.uint64_t, nCtxA int, b *C.crdt_tuples, nbMax int,
+	nbDev, ctxBDev *C.uint64_t, nCtxB int, splittersDev *C.uint64_t, m int, flagsDev *C.uint8_t, out *C.crdt_tuples,
+	srcOutDev *C.int64_t, ctxOutDev, countDev *C.uint64_t) error {
+	if a == nil || b == nil || flagsDev == nil || countDev == nil || naMax < 0 || nbMax < 0 || nCtxA < 0 || nCtxB < 0 || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_orset_merge_causal_ranges(gpuCtx, a, C.size_t(naMax), naDev, ctxADev, C.size_t(nCtxA), b,
+		C.size_t(nbMax), nbDev, ctxBDev, C.size_t(nCtxB), splittersDev, C.size_t(m), flagsDev, out, srcOutDev, ctxOutDev,
+		countDev))
+}
+
+// OrsetMergeCausalRangesCount: the size of that merge alone (nothing stored
+// but the count).
+func OrsetMergeCausalRangesCount(a *C.crdt_tuples, naMax int, naDev, ctxADev *C.uint64_t, nCtxA int, b *C.crdt_tuples,
+	nbMax int, nbDev, ctxBDev *C.uint64_t, nCtxB int, splittersDev *C.uint64_t, m int, flagsDev *C.uint8_t,
+	countDev *C.uint64_t) error {
+	return OrsetMergeCausalRanges(a, naMax, naDev, ctxADev, nCtxA, b, nbMax, nbDev, ctxBDev, nCtxB, splittersDev, m, flagsDev,
+		nil, nil, nil, countDev)
+}
+
 // SetDigest: one order-independent fingerprint per key range of the sorted set
 // state t -- hashOutDev[b] = the wrapping sum of the tuple hash over the
 // tuples of merge(t, {}) whose key falls into bucket b, countOutDev[b] their

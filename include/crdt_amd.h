@@ -473,6 +473,57 @@ int crdt_orset_merge_causal(crdt_ctx *ctx,
                             const uint64_t *ctx_b_dev, size_t n_ctx_b,
                             const crdt_tuples *out, int64_t *src_out_dev, uint64_t *ctx_out_dev,
                             uint64_t *count_dev);
+/* ---- the causal merge restricted to key ranges: digest anti-entropy for the
+ * tombstone-free OR-Set.  crdt_orset_merge_causal is not monotone: a tag a
+ * holds and b's context covers is dropped unless b's copy of it is in the
+ * operand, so merging a with a SELECTION of b (crdt_set_select of the buckets
+ * whose digests differ) would delete tags wherever the replicas already agree.
+ * This call takes the buckets along and does not.
+ * a is the receiver's whole causal state with its context; b is whatever the
+ * peer shipped, normally crdt_set_select(B, CRDT_SET_ORSET, splitters, flags);
+ * ctx_b the peer's WHOLE context.  Buckets are crdt_set_digest's, exactly:
+ * bucket(key) = #{ j : splitters_dev[j] <= key } under unsigned compare, m + 1
+ * buckets, equal neighbouring splitters allowed; m == 0: one bucket
+ * (splitters_dev may then be NULL).  flags_dev[bk] != 0 (m + 1 uint8, e.g.
+ * crdt_set_digest_diff's): bucket bk is flagged.
+ * For a tag g with bucket(g.key) flagged, crdt_orset_merge_causal's rule applies
+ * unchanged.  For a tag g with bucket(g.key) NOT flagged, b is taken to hold
+ * what a holds: g survives iff it is present in a.  b's copies in such a bucket
+ * are ignored entirely -- they add nothing to the tag's state, are never
+ * emitted, are never named by src_out_dev and do not revive a tag tombstoned
+ * on a -- and neither context is read there.
+ * Everything else is crdt_orset_merge_causal's: ascending output, each survivor
+ * once, tomb = 0; src_out_dev's encoding and "the first copy on a side where
+ * the tag is present, a before b"; ctx_out_dev the element-wise maximum,
+ * written whatever the lengths are; out == NULL: the count alone (src_out_dev
+ * NULL too); na_dev / nb_dev (nb_dev: crdt_set_select's count_dev, so the
+ * selection needs no read-back), a value past its n_max storing *count_dev =
+ * ~0 and raising CRDT_DEV_RANGE with out untouched; stream-ordered, no host
+ * synchronisation, workspace from the context only (capturable after
+ * crdt_ctx_reserve); out holds >= na_max + nb_max tuples.
+ * Identities: with every flag set the call equals crdt_orset_merge_causal(a, b)
+ * bit for bit (tuples, src, ctx_out, count); with no flag set it gives a's
+ * present tags and the merged context.  The call is not symmetric in a and b;
+ * a round of it in both directions is (both replicas end with merge(A, B)).
+ * THE CALLER'S OBLIGATION (not enforced), besides crdt_orset_merge_causal's: in
+ * every unflagged bucket the two replicas' canonical OR-Set tuples (canon
+ * below) are equal -- what equal digests say, with probability about 1 - 2^-64
+ * per bucket.
+ * No kernel reads a splitter at or past m or a flag at or past m + 1, whatever
+ * the splitters hold; unsorted splitters are the caller's error: the result is
+ * then unspecified, but every access stays in range.
+ * CRDT_E_INVAL, CRDT_E_RANGE as crdt_orset_merge_causal, and: CRDT_E_INVAL for
+ * flags_dev NULL, splitters_dev NULL with m > 0 or not 8-byte aligned, out /
+ * src_out_dev / ctx_out_dev overlapping the splitters or the flags;
+ * CRDT_E_RANGE for m >= 2^24. */
+int crdt_orset_merge_causal_ranges(crdt_ctx *ctx,
+                                   const crdt_tuples *a, size_t na_max, const uint64_t *na_dev,
+                                   const uint64_t *ctx_a_dev, size_t n_ctx_a,
+                                   const crdt_tuples *b, size_t nb_max, const uint64_t *nb_dev,
+                                   const uint64_t *ctx_b_dev, size_t n_ctx_b,
+                                   const uint64_t *splitters_dev, size_t m, const uint8_t *flags_dev,
+                                   const crdt_tuples *out, int64_t *src_out_dev,
+                                   uint64_t *ctx_out_dev, uint64_t *count_dev);
 /* ---- range digests: find the key ranges in which two set states differ
  * without shipping either (the reference's gossip pull ships the entire Diff
  * every round, main.go:153-170 and :245-256; crdt_set_delta needs both states
