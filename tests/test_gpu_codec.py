@@ -16,6 +16,7 @@ import torch
 from crdt_amd import codec, gossip
 from crdt_amd.refmerge import Command
 from crdt_amd.server import Server
+from codec_util import _decode, _raw_body, _serve, _upload
 from gossip_util import K, KEYS, STRS, _host_round, _pack, _rand_diff, _same_diffs, _state, _unpack
 
 pytestmark = [pytest.mark.gpu, pytest.mark.diag]
@@ -30,51 +31,6 @@ def decode_form(request, eng):
     set_knob(b"codec.small", request.param)
     yield request.param
     set_knob(b"codec.small", 1)
-
-
-def _serve(diff) -> bytes:
-    """The binary gossip body of a Diff (host-only Server: main.go:153-170)."""
-    s = Server(None, 8080)
-    for ts, v in diff.items():
-        s.Diff.Put(ts, v)
-    st, body = s.GossipBinary()
-    s.close()
-    assert st == 200
-    return body
-
-
-def _raw_body(entries):
-    """Hand-built binary body: entries = [(ts, [(k, v), ...] or None)] in the
-    given order (None: a nil map)."""
-    ts, pairs, kl, vl, by = [], [], [], [], b""
-    for t, kv in entries:
-        ts.append(t)
-        pairs.append(0xFFFFFFFF if kv is None else len(kv))
-        for k, v in kv or []:
-            kl.append(len(k))
-            vl.append(len(v))
-            by += k + v
-    n = len(kl)
-    return (b"CRDTSOA1" + struct.pack("<QQQ", len(ts), n, len(by)) + struct.pack(f"<{len(ts)}q", *ts) +
-            struct.pack(f"<{len(ts)}I", *pairs) + struct.pack(f"<{n}I", *kl) + struct.pack(f"<{n}I", *vl) + by)
-
-
-def _upload(eng, bodies):
-    off = np.zeros(len(bodies) + 1, np.int64)
-    off[1:] = np.cumsum([len(b) for b in bodies])
-    blob = b"".join(bodies) or b"\0"
-    return torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(eng.device), off.tolist()
-
-
-def _decode(eng, bodies, keys, vals, key_cap=1 << 20, kv_base=3):
-    data, off = _upload(eng, bodies)
-    ne = sum(codec.body_counts(b)[0] for b in bodies)
-    npairs = sum(codec.body_counts(b)[1] for b in bodies)
-    kk = torch.full((kv_base + npairs + 1,), -1, dtype=torch.int32, device=eng.device)
-    kv = torch.full_like(kk, -1)
-    dec, st = codec.decode(eng, data, off, [1000 * i for i in range(len(bodies))], key_cap, keys, vals, kv_base,
-                           kk, kv, ne)
-    return dec, st, kk.cpu().numpy(), kv.cpu().numpy()
 
 
 _ODD = ["", "x", "\xff\x00", "é", "007", "-0", "\n\t\"<>&", "9223372036854775808"]
