@@ -207,6 +207,8 @@ SIGNATURES = {
                                      _P, _SZ, C.POINTER(crdt_tuples), _P, _P, _P]),
     "crdt_orset_merge_causal_ranges": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, _P, _P, _SZ, C.POINTER(crdt_tuples), _SZ,
                                             _P, _P, _SZ, _P, _SZ, _P, C.POINTER(crdt_tuples), _P, _P, _P]),
+    "crdt_set_apply": (_I, [_CTX, _I, C.POINTER(crdt_tuples), _SZ, _P, _P, _SZ, C.c_uint32, _P, _P, _SZ,
+                            C.POINTER(crdt_tuples), _P, _P, _P]),
     "crdt_set_digest": (_I, [_CTX, _I, C.POINTER(crdt_tuples), _SZ, _P, _P, _SZ, _P, _P]),
     "crdt_set_digest_diff": (_I, [_CTX, _P, _P, _P, _P, _SZ, _P, _P]),
     "crdt_set_select": (_I, [_CTX, _I, C.POINTER(crdt_tuples), _SZ, _P, _P, _SZ, _P, C.POINTER(crdt_tuples), _P,

@@ -1,5 +1,5 @@
 // settile.hpp -- the tile scaffold of the set-state ops (setread, setdelta,
-// setcompact, setdigest, setcausal .hip).  Every one of them
+// setcompact, setdigest, setcausal, setapply .hip).  Every one of them
 // is count / scan / write over tiles of 2048 items with one workspace shape:
 //   tcnt[t]  the tile's output count (under an empty carry)
 //   rec[t]   the tile's carry record (ops whose decisions cross tiles)
@@ -195,11 +195,15 @@ struct TileWs {
     uint64_t *split = nullptr;
     uint32_t *tcnt = nullptr, *rec = nullptr;
     uint64_t *ic = nullptr, *bits = nullptr;
+    // what reserve() asks of the workspace (an op that carves more behind the tiles starts there)
+    static size_t bytes(size_t ntiles, bool with_split, bool with_rec, size_t wpt) {
+        return (with_split ? Carve::round((ntiles + 2) * 8) + 256 : 0) +
+               (with_rec ? 2 : 1) * Carve::round((ntiles + 1) * 4) + Carve::round((ntiles + 1) * 8) +
+               Carve::round((ntiles * wpt + 1) * 8) + 1024;
+    }
     // grows the context's workspace to hold ntiles tiles with wpt bitmap words each, and carves it
-    int reserve(crdt_ctx *ctx, size_t ntiles, bool with_split, bool with_rec, size_t wpt) {
-        const size_t need = (with_split ? Carve::round((ntiles + 2) * 8) + 256 : 0) +
-                            (with_rec ? 2 : 1) * Carve::round((ntiles + 1) * 4) + Carve::round((ntiles + 1) * 8) +
-                            Carve::round((ntiles * wpt + 1) * 8) + 1024;
+    int reserve(crdt_ctx *ctx, size_t ntiles, bool with_split, bool with_rec, size_t wpt, size_t extra = 0) {
+        const size_t need = bytes(ntiles, with_split, with_rec, wpt) + extra;
         const int rc = ws_reserve(ctx, need);
         if (rc) return rc;
         Carve w(ctx->ws);

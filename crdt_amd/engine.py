@@ -642,6 +642,97 @@ class Engine:
         out, src, ctx_out, count = self.causal_merge(a, ctx_a, b, ctx_b, with_src=True)
         return out, self.gather_src(src, a_val, b_val, n_dev=count), ctx_out, count
 
+    # -- the OR-Set mutators: a batch of local adds and removes (crdt_set_apply)
+    def set_apply(self, t: TupleSet, clock: torch.Tensor, rep: int, op_keys: torch.Tensor, op_kinds: torch.Tensor,
+                  causal: bool, n_dev: torch.Tensor | None = None, out: TupleSet | None = None,
+                  src: torch.Tensor | None = None, clock_out: torch.Tensor | None = None,
+                  count: torch.Tensor | None = None, trim: bool = True, with_src: bool = False):
+        """A batch of local operations of replica ``rep`` applied to its
+        sorted OR-Set state ``t``: ``op_keys`` (int64 storage of uint64,
+        non-decreasing) and ``op_kinds`` (uint8: 0 add, else remove) on the
+        device, ``clock`` the replica's clock row / causal context (int64
+        storage of uint64).  Operation i is rep's event clock[rep] + 1 + i,
+        add and remove alike; the result is the batch applied one operation
+        at a time: an add inserts (key, event, rep), a remove tombstones
+        (``causal`` False) or deletes (``causal`` True) every tag of its key
+        held at that point.  Each tag is written once in ascending order,
+        tombstone form with the tomb-OR of its copies then the removes,
+        causal form without the tombstoned tags and with every tomb 0.
+        Returns (out, clock_out, count), or (out, src, clock_out, count) with
+        ``with_src`` (or a ``src`` tensor): out / src of capacity len(t) +
+        len(op_keys), src[i] >= 0 the index in t of the tag's first copy,
+        src[i] < 0 the add at batch index -(src[i] + 1), for
+        :meth:`gather_src`; clock_out = clock with [rep] advanced by the
+        batch's length.  ``n_dev`` as in :meth:`set_elements`; a length out
+        of range, or events that would wrap past 2^64, write nothing but
+        count = ~0 and raise CRDT_DEV_RANGE.  The caller vouches that every
+        tag of rep in t has ts <= clock[rep].  With ``trim`` (the default)
+        the device status is checked and the sliced results returned; without
+        it everything stays on the device, no synchronisation."""
+        n = len(t) + op_keys.numel()
+        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
+        if len(out) < n:
+            raise ValueError("set_apply: out holds fewer tuples than len(t) + len(op_keys)")
+        if src is None and with_src:
+            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        if src is not None:
+            self._check(src, itemsize=8)
+            if src.dtype != torch.int64 or src.numel() < n:
+                raise ValueError("set_apply: src must be int64 and hold len(t) + len(op_keys) entries")
+        clock_out = torch.empty(clock.numel(), dtype=torch.int64, device=self.device) if clock_out is None else clock_out
+        count = self._set_apply(t, clock, rep, op_keys, op_kinds, causal, n_dev, out, src, clock_out, count)
+        if trim:
+            self.check_device()
+            k = int(count.item())
+            return (out.slice(k), clock_out, count) if src is None else (out.slice(k), src[:k], clock_out, count)
+        return (out, clock_out, count) if src is None else (out, src, clock_out, count)
+
+    def set_apply_count(self, t: TupleSet, clock: torch.Tensor, rep: int, op_keys: torch.Tensor,
+                        op_kinds: torch.Tensor, causal: bool, n_dev: torch.Tensor | None = None,
+                        clock_out: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(set_apply(...)) alone (int64[1] on the device, no
+        synchronisation): nothing is written but the count and, when given,
+        ``clock_out``."""
+        return self._set_apply(t, clock, rep, op_keys, op_kinds, causal, n_dev, None, None, clock_out, count)
+
+    def _set_apply(self, t: TupleSet, clock, rep: int, op_keys, op_kinds, causal: bool, n_dev, out, src, clock_out,
+                   count) -> torch.Tensor:
+        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        self._check(count, clock, op_keys, itemsize=8)
+        self._check(op_kinds, itemsize=1)
+        m = op_keys.numel()
+        if op_kinds.numel() != m:
+            raise ValueError("set_apply: one kind per operation key")
+        if not 0 <= rep < 2 ** 32:
+            raise ValueError("set_apply: rep is a uint32")
+        for s in (t,) + (() if out is None else (out,)):
+            self._check(s.key, s.ts, itemsize=8)
+            self._check(s.rep, itemsize=4)
+            self._check(s.tomb, itemsize=1)
+        for x in (n_dev, clock_out):
+            if x is not None:
+                self._check(x, itemsize=8)
+        if clock_out is not None and clock_out.numel() < clock.numel():
+            raise ValueError("set_apply: clock_out holds fewer entries than clock")
+        ct = t.c()
+        co = None if out is None else out.c()
+        self._call("crdt_set_apply", 1 if causal else 0, C.byref(ct), len(t), _ptr(n_dev), _ptr(clock), clock.numel(),
+                   rep, _ptr(op_keys) if m else None, _ptr(op_kinds) if m else None, m,
+                   None if co is None else C.byref(co), _ptr(src), _ptr(clock_out), count.data_ptr())
+        return count
+
+    def map_apply(self, t: TupleSet, val: torch.Tensor, clock: torch.Tensor, rep: int, op_keys: torch.Tensor,
+                  op_kinds: torch.Tensor, op_vals: torch.Tensor, causal: bool):
+        """:meth:`set_apply` of a state that keeps a value beside each tuple
+        (val[i] belongs to t's tuple i, op_vals[i] to operation i; a remove's
+        value is never read): an OR-Map put / delete.  Returns (out, out_val,
+        clock_out, count), device-resident -- the apply, then one
+        :meth:`gather_src` chained off its device count, no read-back."""
+        if val.shape[0] != len(t) or op_vals.shape[0] != op_keys.numel():
+            raise ValueError("map_apply: one value per tuple and per operation")
+        out, src, clock_out, count = self.set_apply(t, clock, rep, op_keys, op_kinds, causal, with_src=True, trim=False)
+        return out, self.gather_src(src, val, op_vals, n_dev=count), clock_out, count
+
     # -- the causal merge restricted to the key ranges whose digests differ
     #    (crdt_orset_merge_causal_ranges)
     def causal_merge_ranges(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet, ctx_b: torch.Tensor | None,

@@ -322,6 +322,43 @@ func OrsetMergeCausalRangesCount(a *C.crdt_tuples, naMax int, naDev, ctxADev *C.
 		nil, nil, nil, countDev)
 }
 
+// SetApply: a batch of local adds and removes applied to the sorted OR-Set
+// state t of replica rep on the device -- the local write (AddCommand,
+// main.go:173-207) for the OR-Set, in the tombstone form (causal false: a
+// remove sets tomb = 1 on the key's tags) or the causal form (causal true: a
+// remove deletes them, every output tomb 0).  clockDev is rep's clock row /
+// causal context (nClock entries); opKeyDev (non-decreasing) and opKindDev (0 =
+// add, else remove) hold the m operations.  Operation i is rep's event
+// clock[rep] + 1 + i, add and remove alike; the result is the batch applied one
+// operation at a time, each tag once in ascending order (capacity nMax + m),
+// its length to countDev.  srcOutDev (nil: not wanted; same capacity) names per
+// output tuple the tag's first copy in t (>= 0) or the add at batch index i as
+// -(i + 1), for GatherSrc; clockOutDev (nil: not wanted; nClock entries) is the
+// clock with [rep] advanced by m.  nDev (nil: all nMax tuples) chains the call
+// off a device count.  The caller vouches that every tag of rep in t has ts <=
+// clock[rep] and that the keys are sorted.  Enqueued: crdt_ctx_sync before
+// reading.
+func SetApply(causal bool, t *C.crdt_tuples, nMax int, nDev, clockDev *C.uint64_t, nClock int, rep uint32,
+	opKeyDev *C.uint64_t, opKindDev *C.uint8_t, m int, out *C.crdt_tuples, srcOutDev *C.int64_t,
+	clockOutDev, countDev *C.uint64_t) error {
+	if t == nil || clockDev == nil || countDev == nil || nMax < 0 || nClock < 0 || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	form := C.int(C.CRDT_APPLY_TOMBSTONE)
+	if causal {
+		form = C.int(C.CRDT_APPLY_CAUSAL)
+	}
+	return status(C.crdt_set_apply(gpuCtx, form, t, C.size_t(nMax), nDev, clockDev, C.size_t(nClock), C.uint32_t(rep),
+		opKeyDev, opKindDev, C.size_t(m), out, srcOutDev, clockOutDev, countDev))
+}
+
+// SetApplyCount: the size of that state alone (nothing stored but the count
+// and, when asked, the advanced clock).
+func SetApplyCount(causal bool, t *C.crdt_tuples, nMax int, nDev, clockDev *C.uint64_t, nClock int, rep uint32,
+	opKeyDev *C.uint64_t, opKindDev *C.uint8_t, m int, clockOutDev, countDev *C.uint64_t) error {
+	return SetApply(causal, t, nMax, nDev, clockDev, nClock, rep, opKeyDev, opKindDev, m, nil, nil, clockOutDev, countDev)
+}
+
 // SetDigest: one order-independent fingerprint per key range of the sorted set
 // state t -- hashOutDev[b] = the wrapping sum of the tuple hash over the
 // tuples of merge(t, {}) whose key falls into bucket b, countOutDev[b] their

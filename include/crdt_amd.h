@@ -446,8 +446,11 @@ int crdt_set_compact(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max
  * crdt_set_compact's contract).  Under these the merge is commutative (equal
  * tuples and equal ctx_out for either operand order), associative and
  * idempotent (merge(A, A) = A's present tags), and (out, ctx_out) is again
- * such a state.  Local adds and removes are the host's: an add appends (key,
- * ++ctx[r], r), a remove deletes the key's tuples and leaves the context.
+ * such a state.  Local adds and removes are crdt_set_apply's (below): every
+ * operation of replica r, add and remove alike, is r's next event ++ctx[r]; an
+ * add inserts (key, that event, r), a remove deletes the key's tuples, and an
+ * event number with no tag is "seen and removed", so the context stays
+ * contiguous.
  * na_dev / nb_dev follow crdt_set_delta's ns_dev, each on its own: NULL -> all
  * n_max tuples of the side; <= n_max -> the first so many; > n_max on either
  * side -> no tuple of either side is touched, nothing is written to out or
@@ -524,6 +527,75 @@ int crdt_orset_merge_causal_ranges(crdt_ctx *ctx,
                                    const uint64_t *splitters_dev, size_t m, const uint8_t *flags_dev,
                                    const crdt_tuples *out, int64_t *src_out_dev,
                                    uint64_t *ctx_out_dev, uint64_t *count_dev);
+/* ---- the OR-Set mutators: a batch of local adds and removes applied on the
+ * device (the reference's local write, AddCommand, main.go:173-207, is
+ * crdt_local_apply for its log; this is the same step for the OR-Set, in the
+ * tombstone form and in the causal form).  An LWW add or remove needs no call
+ * of its own: it is a one-tuple state under crdt_lww_merge.
+ * t is a state sorted ascending by (key, ts, rep), copies of one tag in any
+ * order and number, its length n_max / n_dev as in crdt_set_compact.  rep is
+ * the applying replica and clock_dev[0 .. n_clock) its clock row -- a
+ * vector-clock row or a causal context, the same thing here.  The batch is m
+ * operations (m a host value): op_key_dev[m] uint64, NON-DECREASING, and
+ * op_kind_dev[m] uint8, 0 = add, nonzero = remove.  form is
+ * CRDT_APPLY_TOMBSTONE or CRDT_APPLY_CAUSAL.
+ * The result is the batch applied one operation at a time in index order.
+ * With ts0 = clock[rep] (read on the device), operation i is event e_i = ts0 +
+ * 1 + i of rep: EVERY operation is an event, add and remove alike, in both
+ * forms -- so ts counts rep's events as crdt_set_compact's contract asks, and
+ * a causal context stays contiguous (an event number with no tag is "seen and
+ * removed").
+ *   add(k)     inserts the tag (k, e_i, rep) with tomb 0.
+ *   remove(k)  tombstone form: sets tomb = 1 on every tag of k held at that
+ *              point, tags added earlier in the batch included;
+ *              causal form: deletes every tag of k held at that point.
+ * The output is canonical, as crdt_set_compact(t, no cut) /
+ * crdt_orset_merge_causal write it: each tag once, in ascending tuple order;
+ * tombstone form: tomb = the OR over the tag's copies, then the removes;
+ * causal form: a tag whose tomb-OR in t is 1 counts as absent and is dropped,
+ * and every output tomb is 0.  In closed form (what the kernels compute): a
+ * tag of t is tombstoned / dropped iff the batch holds any remove of its key;
+ * the tag of add i iff a remove of its key sits at an index > i; the output is
+ * the sorted union of the survivors.
+ * out holds >= n_max + m tuples; *count_dev (device uint64) receives the
+ * length.  src_out_dev (may be NULL; n_max + m int64): per output tuple >= 0
+ * the index in t of the tag's first copy (crdt_set_compact's choice), or -(i +
+ * 1) for the add at batch index i, so crdt_src_gather(src, n_max + m,
+ * count_dev, state values, n, per-operation values, m, ...) moves a value
+ * column: an OR-Map put with no read-back.  clock_out_dev (may be NULL;
+ * n_clock uint64) = clock with [rep] = ts0 + m.  out may be NULL: the count
+ * alone; src_out_dev must then be NULL too, clock_out_dev is still written.
+ * Poison: *n_dev > n_max, or ts0 + m wrapping past 2^64, touches no tuple,
+ * stores *count_dev = ~0 and raises CRDT_DEV_RANGE; out, src_out_dev and
+ * clock_out_dev are left as they were.
+ * THE CALLER'S OBLIGATION (not enforced): every tag of rep in t has ts <=
+ * clock[rep], so a new tag never equals an existing one; the operation keys
+ * are non-decreasing.  If either is broken the result is unspecified, but
+ * every access stays in range.
+ * Identities: m == 0, tombstone form: crdt_orset_merge_src(t, {}) bit for bit
+ * (tuples, src, count); m == 0, causal form: the tuples of
+ * crdt_orset_merge_causal(t, clock, {}, no context); an adds-only batch,
+ * tombstone form: crdt_orset_merge(t, the batch's tags) bit for bit.
+ * Stream-ordered, no host synchronisation; workspace from the context only
+ * (capturable after crdt_ctx_reserve).  No kernel reads t at or past
+ * min(*n_dev, n_max), an operation at or past m or the clock at or past
+ * n_clock.  key / ts / rep naturally aligned but otherwise at arbitrary
+ * offsets.
+ * CRDT_E_INVAL: NULL ctx / t / count_dev / clock_dev, rep >= n_clock, a bad
+ * form, NULL fields of t with n_max > 0 or of out with n_max + m > 0, NULL
+ * operation arrays with m > 0, key / ts / rep of t or out not naturally
+ * aligned, op_key_dev, clock_dev, clock_out_dev, src_out_dev, n_dev or
+ * count_dev not 8-byte aligned, src_out_dev without out, any output
+ * overlapping any input or another output; CRDT_E_RANGE: n_max or m >= 2^62,
+ * n_clock >= 2^32, or more tiles than a launch holds.  n_max + m == 0 launches
+ * nothing but the count store and the clock write. */
+#define CRDT_APPLY_TOMBSTONE 0
+#define CRDT_APPLY_CAUSAL 1
+int crdt_set_apply(crdt_ctx *ctx, int form, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
+                   const uint64_t *clock_dev, size_t n_clock, uint32_t rep,
+                   const uint64_t *op_key_dev, const uint8_t *op_kind_dev, size_t m,
+                   const crdt_tuples *out, int64_t *src_out_dev, uint64_t *clock_out_dev,
+                   uint64_t *count_dev);
 /* ---- range digests: find the key ranges in which two set states differ
  * without shipping either (the reference's gossip pull ships the entire Diff
  * every round, main.go:153-170 and :245-256; crdt_set_delta needs both states
