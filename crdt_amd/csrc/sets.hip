@@ -13,8 +13,8 @@
 //
 // GPU structure: two passes over merge-order bitmaps, no cross-workgroup
 // waiting:
-//   split  : merge-path splits of every tile (16-ary searches, four tile
-//            diagonals per wave);
+//   split  : merge-path splits of every tile (k_mp_split of settile.hpp:
+//            16-ary searches, four tile diagonals per wave);
 //   count  : per tile the merge in LDS -> two bitmaps in merge order (`isa`:
 //            the item is an A element; `emit`: the item is an output) and the
 //            tile's output count;
@@ -28,10 +28,16 @@
 // Cache for the write pass, and a second stream running chunk c+1's count
 // beside chunk c's write, measured slower: DESIGN.md §5.4.1.  So did one
 // pass with a decoupled look-back, §5.4.4.)
+// The lengths' checks, the workspace (TileWs), the split and its search are
+// settile.hpp's, shared with the set-state ops; both modes run through one
+// host driver (merge_two_pass).  The count, scan and write kernels are this
+// file's own, and their text is kept as it is: their instructions are the
+// measured ones.
 #include <algorithm>
 #include <atomic>
 
 #include "scan.hpp"
+#include "settile.hpp"
 
 namespace crdt {
 
@@ -52,15 +58,6 @@ __device__ __forceinline__ Tag tag_sel(bool c, const Tag &x, const Tag &y) {
     return Tag{c ? x.k : y.k, c ? x.t : y.t, c ? x.r : y.r};
 }
 __device__ __forceinline__ Tag gtag(const crdt_tuples &s, size_t i) { return Tag{s.key[i], s.ts[i], s.rep[i]}; }
-
-// A[i] <= B[j] in tuple order, reading ts / rep only on a tie.
-__device__ __forceinline__ bool g_le_lazy(const crdt_tuples &A, size_t i, const crdt_tuples &B, size_t j) {
-    const uint64_t ka = A.key[i], kb = B.key[j];
-    if (ka != kb) return ka < kb;
-    const uint64_t ta = A.ts[i], tb = B.ts[j];
-    if (ta != tb) return ta < tb;
-    return A.rep[i] <= B.rep[j];
-}
 
 // A write pass derives every staged run and index from its tile's bitmaps
 // (lane w < nw holds word w of each): they must set no bit at or past the
@@ -84,7 +81,8 @@ __device__ __forceinline__ bool bitmaps_consistent(uint64_t word_a, uint64_t wor
 // first element in the stable merged order carrying the key's max tag).  So
 // the merge runs over KEYS only (A first on an equal key), and only the run
 // ends' ts / rep / tomb are ever read:
-//   k_lww_split : merge-path splits of 4096-item tiles over the keys;
+//   k_mp_split  : merge-path splits of 4096-item tiles over the keys
+//                 (settile.hpp, TupleLe<true>);
 //   k_lww_count : per tile, the keys staged in LDS by LDS-DMA and merged
 //                 (512 threads x 8 items): bitmap `isa` (merge item is an A
 //                 element) and `emit` (its key differs from the next merged
@@ -103,47 +101,19 @@ constexpr int LCB = 512;                 // count pass threads (8 items each)
 constexpr int LNW = LT / 64;             // bitmap words per tile and bitmap
 constexpr uint32_t kScanMax = 16384;     // tiles per chunk (one scan workgroup)
 
-template <int TT = LT>
-__global__ __launch_bounds__(256) void k_lww_split(const uint64_t *__restrict__ ka, const uint64_t *__restrict__ kb,
-                                                   size_t na, size_t nb, size_t ntiles, uint64_t *__restrict__ split) {
-    const int lane = threadIdx.x & 63, grp = lane >> 4, gl = lane & 15;
-    const size_t t = ((((size_t)blockIdx.x * 256 + threadIdx.x) >> 6) << 2) + (size_t)grp;
-    const size_t n = na + nb;
-    const size_t d = t * TT < n ? t * TT : n;
-    size_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
-    bool done = t > ntiles || hi <= lo;
-    // P(i) = A.key[i] <= B.key[d-1-i]: true below the split, false from it
-    while (__ballot(!done)) {
-        const size_t span = hi - lo;
-        const bool small = span <= 16;
-        const size_t c = small ? lo + (size_t)gl : lo + ((size_t)gl * span) / 16;
-        const bool valid = !done && (small ? (size_t)gl < span : true);
-        const bool p = valid && ka[c] <= kb[d - 1 - c];
-        const unsigned m = (unsigned)((__ballot(p) >> (grp * 16)) & 0xFFFF);
-        const unsigned cnt = (unsigned)__popc(m);
-        if (!done) {
-            if (small) {
-                lo += cnt;
-                done = true;
-            } else {
-                const size_t nlo = cnt > 0 ? lo + (((size_t)(cnt - 1)) * span) / 16 + 1 : lo;
-                const size_t nhi = cnt < 16 ? lo + ((size_t)cnt * span) / 16 : hi;
-                lo = nlo;
-                hi = nhi;
-                done = hi <= lo;
-            }
-        }
-    }
-    if (gl == 0 && t <= ntiles) split[t] = lo;
-}
+// the scaffold's tile count is for 2048-item tiles: LWW's are twice that
+struct LwwTiles {
+    static __device__ __forceinline__ uint64_t tiles(uint64_t na, uint64_t nb) { return (na + nb + LT - 1) / LT; }
+};
 
-struct LwwTile {
+// Tile t of TT merge items out of n: A's run [i0, i1) and B's [j0, j1) from the splits.
+struct MergeTile {
     size_t i0, i1, j0, j1;
     uint32_t na, nb, n;
 };
-template <int TT = LT>
-__device__ __forceinline__ LwwTile lww_tile(const uint64_t *__restrict__ split, uint64_t t, size_t n) {
-    LwwTile b;
+template <int TT>
+__device__ __forceinline__ MergeTile merge_tile(const uint64_t *__restrict__ split, uint64_t t, size_t n) {
+    MergeTile b;
     const size_t d0 = (size_t)t * TT, d1 = d0 + TT < n ? d0 + TT : n;
     b.i0 = split[t];
     b.i1 = split[t + 1];
@@ -163,7 +133,7 @@ __global__ __launch_bounds__(LCB) void k_lww_count(const uint64_t *__restrict__ 
     __shared__ alignas(16) uint64_t sk[LT + 8];          // A's run, then B's, each from its 16-byte aligned-down start
     __shared__ uint32_t s_w[LCB / 64];
     const uint64_t t = t0 + blockIdx.x;
-    const LwwTile b = lww_tile(split, t, na + nb);
+    const MergeTile b = merge_tile<LT>(split, t, na + nb);
     const int lane0 = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t at = 0;
     const int oa = dma_run<uint64_t, LCB / 64>(ka, b.i0, b.na, sk, &at, wv, lane0);
@@ -343,8 +313,9 @@ __global__ __launch_bounds__(WT) void k_lww_write_src(crdt_tuples A, crdt_tuples
 // (key, ts, rep) in tag order, its tomb the OR over every copy; in the
 // stable merge (A first on an equal tag) a tag's copies are consecutive --
 // A's, then B's -- so the first copy emits:
-//   k_or_split : merge-path splits of 2048-item tiles over the tags;
-//   k_or_count : per tile the tags merged in LDS (512 threads x 4 items):
+//   k_mp_split : merge-path splits of 2048-item tiles over the tags
+//                (settile.hpp, TupleLe<false>);
+//   k_or_count_dma : per tile the tags merged in LDS (512 threads x 4 items):
 //                bitmaps `isa` and `emit` (the item's tag differs from the
 //                previous merged tag), 512 B per tile, the emit count;
 //   k_chunk_scan;
@@ -358,72 +329,42 @@ constexpr int OCB = 512;                 // count pass threads (4 items each; 25
 constexpr int OWT = 512;                 // write pass threads (4 items each)
 constexpr int ONW = OT / 64;             // bitmap words per tile and bitmap
 
-// The merge-path split of diagonal t * OT (one 16-lane group per diagonal,
-// four per wave; every lane of the wave calls it: the ballots are wave-wide).
-__device__ __forceinline__ void or_split_diag(const crdt_tuples &A, const crdt_tuples &B, size_t na, size_t nb,
-                                              size_t ntiles, size_t t, uint64_t *__restrict__ split) {
-    const int lane = threadIdx.x & 63, grp = lane >> 4, gl = lane & 15;
-    const size_t n = na + nb;
-    const size_t d = t * OT < n ? t * OT : n;
-    size_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
-    bool done = t > ntiles || hi <= lo;
-    while (__ballot(!done)) {
-        const size_t span = hi - lo;
-        const bool small = span <= 16;
-        const size_t c = small ? lo + (size_t)gl : lo + ((size_t)gl * span) / 16;
-        const bool valid = !done && (small ? (size_t)gl < span : true);
-        const bool p = valid && g_le_lazy(A, c, B, d - 1 - c);
-        const unsigned m = (unsigned)((__ballot(p) >> (grp * 16)) & 0xFFFF);
-        const unsigned cnt = (unsigned)__popc(m);
-        if (!done) {
-            if (small) {
-                lo += cnt;
-                done = true;
-            } else {
-                const size_t nlo = cnt > 0 ? lo + (((size_t)(cnt - 1)) * span) / 16 + 1 : lo;
-                const size_t nhi = cnt < 16 ? lo + ((size_t)cnt * span) / 16 : hi;
-                lo = nlo;
-                hi = nhi;
-                done = hi <= lo;
-            }
-        }
-    }
-    if (gl == 0 && t <= ntiles) split[t] = lo;
-}
-
-__global__ __launch_bounds__(256) void k_or_split(crdt_tuples A, crdt_tuples B, size_t na, size_t nb, size_t ntiles,
-                                                  uint64_t *__restrict__ split) {
-    const size_t t = ((((size_t)blockIdx.x * 256 + threadIdx.x) >> 6) << 2) + (size_t)((threadIdx.x & 63) >> 4);
-    or_split_diag(A, B, na, nb, ntiles, t, split);
-}
-
-__device__ __forceinline__ LwwTile or_tile(const uint64_t *__restrict__ split, uint64_t t, size_t n) {
-    LwwTile b;
-    const size_t d0 = (size_t)t * OT, d1 = d0 + OT < n ? d0 + OT : n;
-    b.i0 = split[t];
-    b.i1 = split[t + 1];
-    b.j0 = d0 - b.i0;
-    b.j1 = d1 - b.i1;
-    b.na = (uint32_t)(b.i1 - b.i0);
-    b.nb = (uint32_t)(b.j1 - b.j0);
-    b.n = b.na + b.nb;
-    return b;
-}
-
-template <int NT>
-__global__ __launch_bounds__(NT) void k_or_count(crdt_tuples A, crdt_tuples B, size_t na, size_t nb,
-                                                 const uint64_t *__restrict__ split, uint32_t *__restrict__ tcnt,
-                                                 uint64_t *__restrict__ bits, uint64_t t0) {
+// The count pass.  The tile's key / ts / rep are staged in LDS, each side's
+// run from the element before the tile (the first item's merged predecessor
+// candidate): element x of the tile's A run (x >= -1) is at field index
+// oa_f + x, B's at ob_f + x.
+//   DMA (sets.or_count_dma, the default): by LDS-DMA, each run from its
+//       16-byte aligned-down start, the element before it only when there is
+//       one: no VGPR round trip;
+//   else: through registers, A[i0-1], A's run, B[j0-1], B's run at slots 0 ..
+//       (a missing predecessor staged as 0, never used).
+// One merge, the same bitmaps.
+template <int NT, bool DMA>
+__global__ __launch_bounds__(NT) void k_or_count_dma(crdt_tuples A, crdt_tuples B, size_t na, size_t nb,
+                                                     const uint64_t *__restrict__ split, uint32_t *__restrict__ tcnt,
+                                                     uint64_t *__restrict__ bits, uint64_t t0) {
     constexpr int NI = OT / NT, LPW = 64 / NI, CAP = OT + 2;
-    // staged: A[i0-1], A part, B[j0-1], B part (slot 0 of each side: the
-    // element before the tile, the first item's merged predecessor candidate)
-    __shared__ uint64_t sk[CAP], st[CAP];
-    __shared__ uint32_t sr[CAP];
+    __shared__ alignas(16) uint64_t sk[CAP + 8], st[CAP + 8];
+    __shared__ alignas(16) uint32_t sr[CAP + 16];
     __shared__ uint32_t s_w[NT / 64];
     const uint64_t t = t0 + blockIdx.x;
-    const LwwTile b = or_tile(split, t, na + nb);
-    const uint32_t nsa = b.na + 1, nst = nsa + b.nb + 1;
-    {
+    const MergeTile b = merge_tile<OT>(split, t, na + nb);
+    int oa_k, ob_k, oa_t, ob_t, oa_r, ob_r;
+    if constexpr (DMA) {
+        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), ln = threadIdx.x & 63;
+        const uint32_t pa = b.i0 > 0 ? 1u : 0u, pb = b.j0 > 0 ? 1u : 0u;
+        uint32_t at = 0;
+        oa_k = dma_run<uint64_t, NT / 64>(A.key, b.i0 - pa, b.na + pa, sk, &at, wv, ln) + (int)pa;
+        ob_k = dma_run<uint64_t, NT / 64>(B.key, b.j0 - pb, b.nb + pb, sk, &at, wv, ln) + (int)pb;
+        at = 0;
+        oa_t = dma_run<uint64_t, NT / 64>(A.ts, b.i0 - pa, b.na + pa, st, &at, wv, ln) + (int)pa;
+        ob_t = dma_run<uint64_t, NT / 64>(B.ts, b.j0 - pb, b.nb + pb, st, &at, wv, ln) + (int)pb;
+        at = 0;
+        oa_r = dma_run<uint32_t, NT / 64>(A.rep, b.i0 - pa, b.na + pa, sr, &at, wv, ln) + (int)pa;
+        ob_r = dma_run<uint32_t, NT / 64>(B.rep, b.j0 - pb, b.nb + pb, sr, &at, wv, ln) + (int)pb;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA has landed in LDS
+    } else {
+        const uint32_t nsa = b.na + 1, nst = nsa + b.nb + 1;
         uint64_t k[NI + 1], ts[NI + 1];
         uint32_t r[NI + 1];
 #pragma unroll
@@ -445,101 +386,9 @@ __global__ __launch_bounds__(NT) void k_or_count(crdt_tuples A, crdt_tuples B, s
                 sr[x] = r[j];
             }
         }
+        oa_k = oa_t = oa_r = 1;
+        ob_k = ob_t = ob_r = (int)nsa + 1;
     }
-    __syncthreads();
-    // side views: A element a of the tile at slot 1 + a, B element j at nsa + 1 + j
-#define OA(x) Tag{sk[1 + (x)], st[1 + (x)], sr[1 + (x)]}
-#define OB(x) Tag{sk[nsa + 1 + (x)], st[nsa + 1 + (x)], sr[nsa + 1 + (x)]}
-    const uint32_t k0 = threadIdx.x * NI < b.n ? threadIdx.x * NI : b.n;
-    const uint32_t k1 = k0 + NI < b.n ? k0 + NI : b.n;
-    uint32_t isa = 0, emit = 0;
-    if (k0 < k1) {
-        uint32_t lo = k0 > b.nb ? k0 - b.nb : 0, hi = k0 < b.na ? k0 : b.na;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            const uint64_t ka = sk[1 + mid], kb = sk[nsa + 1 + (k0 - 1 - mid)];
-            const bool le = ka != kb ? ka < kb : tag_le(OA(mid), OB(k0 - 1 - mid));
-            if (le) lo = mid + 1;
-            else hi = mid;
-        }
-        uint32_t ia = lo, ib = k0 - lo;
-        // the merged predecessor of item k0: the later of A[ia-1], B[ib-1]
-        // (A first on an equal tag), each possibly the element before the tile
-        const bool hpa = b.i0 + ia > 0, hpb = b.j0 + ib > 0;
-        const Tag pa{sk[ia], st[ia], sr[ia]}, pb{sk[nsa + ib], st[nsa + ib], sr[nsa + ib]};
-        bool has_prev = hpa || hpb;
-        Tag prev = tag_sel(hpa && hpb ? tag_le(pa, pb) : !hpa, pb, pa);
-        Tag ha = ia < b.na ? OA(ia) : Tag{0, 0, 0}, hb = ib < b.nb ? OB(ib) : Tag{0, 0, 0};
-        for (uint32_t i = 0; i < k1 - k0; ++i) {
-            const bool take_a = ia < b.na && (ib >= b.nb || tag_le(ha, hb));
-            const Tag cur = tag_sel(take_a, ha, hb);
-            if (!has_prev || !tag_eq(prev, cur)) emit |= 1u << i;
-            prev = cur;
-            has_prev = true;
-            if (take_a) {
-                isa |= 1u << i;
-                ++ia;
-                if (ia < b.na) ha = OA(ia);
-            } else {
-                ++ib;
-                if (ib < b.nb) hb = OB(ib);
-            }
-        }
-    }
-#undef OA
-#undef OB
-    const int lane = threadIdx.x & 63, sh = (lane % LPW) * NI;
-    uint64_t wl = (uint64_t)isa << sh, we = (uint64_t)emit << sh;
-#pragma unroll
-    for (int o = 1; o < LPW; o <<= 1) {
-        wl |= (uint64_t)__shfl_xor((unsigned long long)wl, o);
-        we |= (uint64_t)__shfl_xor((unsigned long long)we, o);
-    }
-    if (lane % LPW == 0) {
-        const uint32_t w = threadIdx.x / LPW;
-        bits[t * 2 * ONW + w] = wl;
-        bits[t * 2 * ONW + ONW + w] = we;
-    }
-    uint32_t x = (uint32_t)__popc(emit);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    if (lane == 0) s_w[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t tot = 0;
-#pragma unroll
-        for (int k = 0; k < NT / 64; ++k) tot += s_w[k];
-        tcnt[t] = tot;
-    }
-}
-
-// k_or_count with the tile's key / ts / rep staged by LDS-DMA (each side's
-// run from the element before the tile, from its 16-byte aligned-down start:
-// no VGPR round trip; sets.or_count_dma).  Same merge, same bitmaps.
-template <int NT>
-__global__ __launch_bounds__(NT) void k_or_count_dma(crdt_tuples A, crdt_tuples B, size_t na, size_t nb,
-                                                     const uint64_t *__restrict__ split, uint32_t *__restrict__ tcnt,
-                                                     uint64_t *__restrict__ bits, uint64_t t0) {
-    constexpr int NI = OT / NT, LPW = 64 / NI, CAP = OT + 2;
-    __shared__ alignas(16) uint64_t sk[CAP + 8], st[CAP + 8];
-    __shared__ alignas(16) uint32_t sr[CAP + 16];
-    __shared__ uint32_t s_w[NT / 64];
-    const uint64_t t = t0 + blockIdx.x;
-    const LwwTile b = or_tile(split, t, na + nb);
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), ln = threadIdx.x & 63;
-    // each side from the element before the tile (when there is one): element
-    // x of the tile's A run (x >= -1) is at field index oa_f + x
-    const uint32_t pa = b.i0 > 0 ? 1u : 0u, pb = b.j0 > 0 ? 1u : 0u;
-    uint32_t at = 0;
-    const int oa_k = dma_run<uint64_t, NT / 64>(A.key, b.i0 - pa, b.na + pa, sk, &at, wv, ln) + (int)pa;
-    const int ob_k = dma_run<uint64_t, NT / 64>(B.key, b.j0 - pb, b.nb + pb, sk, &at, wv, ln) + (int)pb;
-    at = 0;
-    const int oa_t = dma_run<uint64_t, NT / 64>(A.ts, b.i0 - pa, b.na + pa, st, &at, wv, ln) + (int)pa;
-    const int ob_t = dma_run<uint64_t, NT / 64>(B.ts, b.j0 - pb, b.nb + pb, st, &at, wv, ln) + (int)pb;
-    at = 0;
-    const int oa_r = dma_run<uint32_t, NT / 64>(A.rep, b.i0 - pa, b.na + pa, sr, &at, wv, ln) + (int)pa;
-    const int ob_r = dma_run<uint32_t, NT / 64>(B.rep, b.j0 - pb, b.nb + pb, sr, &at, wv, ln) + (int)pb;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA has landed in LDS
     __syncthreads();
 #define OA(x) Tag{sk[oa_k + (int)(x)], st[oa_t + (int)(x)], sr[oa_r + (int)(x)]}
 #define OB(x) Tag{sk[ob_k + (int)(x)], st[ob_t + (int)(x)], sr[ob_r + (int)(x)]}
@@ -659,89 +508,90 @@ static int two_pass(crdt_ctx *ctx, size_t ntiles, uint64_t *out_count, CountF co
     return check_launch(ctx);
 }
 
-// (src != nullptr: the _src write kernels, every output's source index beside it)
-static int lww_merge_keyruns(crdt_ctx *ctx, const crdt_tuples &A, size_t na, const crdt_tuples &B, size_t nb,
-                             const crdt_tuples &O, int64_t *src, uint64_t *out_count) {
-    const size_t n = na + nb;
-    const size_t ntiles = (n + LT - 1) / LT;
-    if (ntiles >= 0x7fffffffULL || n >= (1ULL << 62)) return CRDT_E_RANGE;
-    const size_t need = Carve::round((ntiles + 1) * 8) + Carve::round(ntiles * 4 + 4) + Carve::round((ntiles + 1) * 8) +
-                        Carve::round(ntiles * 2 * LNW * 8) + 1024;
-    int rc = ws_reserve(ctx, need);
-    if (rc) return rc;
-    Carve w(ctx->ws);
-    uint64_t *split = w.take<uint64_t>(ntiles + 1);
-    uint32_t *tcnt = w.take<uint32_t>(ntiles + 1);
-    uint64_t *ic = w.take<uint64_t>(ntiles + 1);
-    uint64_t *bits = w.take<uint64_t>(ntiles * 2 * LNW);
-    uint32_t *err = ctx->dev_status;
-    const uint64_t *ka = A.key, *kb = B.key;             // (nullptr for an empty side: never dereferenced)
-    k_lww_split<<<(unsigned)((ntiles + 1 + 15) / 16), 256, 0, ctx->stream>>>(ka, kb, na, nb, ntiles, split);
-    // write-pass workgroups per tile (sets.lww_parts): 1/P of a tile's items, 4 per thread
-    const unsigned P = (unsigned)g_lww_parts;
-    auto cnt = [&](size_t t0, uint32_t nt, hipStream_t s) {
-        k_lww_count<<<nt, LCB, 0, s>>>(ka, kb, na, nb, split, tcnt, bits, t0);
-    };
-    auto scn = [&](size_t t0, uint32_t nt, uint64_t *c, hipStream_t s) {
-        k_chunk_scan<<<1, 1024, 0, s>>>(tcnt, t0, nt, ic, c);
-    };
-    auto wr = [&](size_t t0, uint32_t nt, hipStream_t s) {
-        const unsigned g = P * nt;
-        if (src) {
-            if (P == 2) k_lww_write_src<2048, 512><<<g, 512, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
-            else if (P == 8) k_lww_write_src<512, 128><<<g, 128, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
-            else if (P == 16) k_lww_write_src<256, 64><<<g, 64, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
-            else k_lww_write_src<1024, 256><<<g, 256, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
-            return;
-        }
-        if (P == 2) k_lww_write<2048, 512><<<g, 512, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
-        else if (P == 8) k_lww_write<512, 128><<<g, 128, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
-        else if (P == 16) k_lww_write<256, 64><<<g, 64, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
-        else k_lww_write<1024, 256><<<g, 256, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
-    };
-    return two_pass(ctx, ntiles, out_count, cnt, scn, wr, (size_t)g_lww_chunk, take_fail_zero_bits(), bits,
-                    ntiles * 2 * LNW * 8);
-}
+// What the passes of one merge call take (src != nullptr: the _src write
+// kernels, every output's source index beside it).
+struct MergeCall {
+    crdt_tuples A, B, O;
+    size_t na, nb;
+    int64_t *src;
+    uint32_t *err;
+    TileWs w;
+};
 
-static int orset_merge_twopass(crdt_ctx *ctx, const crdt_tuples &A, size_t na, const crdt_tuples &B, size_t nb,
-                               const crdt_tuples &O, int64_t *src, uint64_t *out_count) {
+// The two modes of the two-pass merge.  A mode gives its tile (kT merge items,
+// kNW words per bitmap), the split's order and tile count, its chunk knob, and
+// the count and write launches of the tiles t0 .. t0 + nt.  A write pass takes
+// 1/P of a tile per workgroup (sets.lww_parts / sets.or_parts), 4 items per thread.
+struct LwwMode {
+    static constexpr int kT = LT, kNW = LNW;
+    using Le = TupleLe<true>;
+    using Tiles = LwwTiles;
+    static size_t chunk() { return (size_t)g_lww_chunk; }
+    static void count(const MergeCall &m, size_t t0, uint32_t nt, hipStream_t s) {
+        k_lww_count<<<nt, LCB, 0, s>>>(m.A.key, m.B.key, m.na, m.nb, m.w.split, m.w.tcnt, m.w.bits, t0);
+    }
+    template <int WH, int WT>
+    static void part(const MergeCall &m, size_t t0, unsigned g, hipStream_t s) {
+        if (m.src)
+            k_lww_write_src<WH, WT><<<g, WT, 0, s>>>(m.A, m.B, m.na, m.nb, m.w.split, m.w.bits, m.w.ic, m.O, m.src, t0,
+                                                     m.err);
+        else k_lww_write<WH, WT><<<g, WT, 0, s>>>(m.A, m.B, m.na, m.nb, m.w.split, m.w.bits, m.w.ic, m.O, t0, m.err);
+    }
+    static void write(const MergeCall &m, size_t t0, uint32_t nt, hipStream_t s) {
+        const unsigned P = (unsigned)g_lww_parts, g = P * nt;
+        if (P == 2) part<2048, 512>(m, t0, g, s);
+        else if (P == 8) part<512, 128>(m, t0, g, s);
+        else if (P == 16) part<256, 64>(m, t0, g, s);
+        else part<1024, 256>(m, t0, g, s);
+    }
+};
+
+struct OrMode {
+    static constexpr int kT = OT, kNW = ONW;
+    using Le = TupleLe<false>;
+    using Tiles = PlainTiles;
+    static size_t chunk() { return (size_t)g_or_chunk; }
+    static void count(const MergeCall &m, size_t t0, uint32_t nt, hipStream_t s) {
+        if (g_or_count_dma)
+            k_or_count_dma<OCB, true><<<nt, OCB, 0, s>>>(m.A, m.B, m.na, m.nb, m.w.split, m.w.tcnt, m.w.bits, t0);
+        else k_or_count_dma<OCB, false><<<nt, OCB, 0, s>>>(m.A, m.B, m.na, m.nb, m.w.split, m.w.tcnt, m.w.bits, t0);
+    }
+    template <int WH, int WT>
+    static void part(const MergeCall &m, size_t t0, unsigned g, hipStream_t s) {
+        if (m.src)
+            k_or_write_src<WH, WT><<<g, WT, 0, s>>>(m.A, m.B, m.na, m.nb, m.w.split, m.w.bits, m.w.ic, m.O, m.src, t0,
+                                                    m.err);
+        else k_or_write<WH, WT><<<g, WT, 0, s>>>(m.A, m.B, m.na, m.nb, m.w.split, m.w.bits, m.w.ic, m.O, t0, m.err);
+    }
+    static void write(const MergeCall &m, size_t t0, uint32_t nt, hipStream_t s) {
+        const unsigned P = (unsigned)g_or_parts, g = P * nt;
+        if (P == 2) part<1024, 256>(m, t0, g, s);
+        else if (P == 4) part<512, 128>(m, t0, g, s);
+        else part<2048, 512>(m, t0, g, s);
+    }
+};
+static_assert(OT == kTile, "PlainTiles counts the OR-Set's tiles");
+
+// One merge: the splits of every tile, then the chunked count / scan / write.
+// (An empty side's columns are null: never dereferenced.)
+template <class M>
+static int merge_two_pass(crdt_ctx *ctx, const crdt_tuples &A, size_t na, const crdt_tuples &B, size_t nb,
+                          const crdt_tuples &O, int64_t *src, uint64_t *out_count) {
     const size_t n = na + nb;
-    const size_t ntiles = (n + OT - 1) / OT;
+    const size_t ntiles = (n + M::kT - 1) / M::kT;
     if (ntiles >= 0x7fffffffULL || n >= (1ULL << 62)) return CRDT_E_RANGE;
-    const size_t need = Carve::round((ntiles + 1) * 8) + Carve::round(ntiles * 4 + 4) + Carve::round((ntiles + 1) * 8) +
-                        Carve::round(ntiles * 2 * ONW * 8) + 1024;
-    int rc = ws_reserve(ctx, need);
+    MergeCall m{A, B, O, na, nb, src, ctx->dev_status, {}};
+    const int rc = m.w.reserve(ctx, ntiles, true, false, 2 * M::kNW);
     if (rc) return rc;
-    Carve w(ctx->ws);
-    uint64_t *split = w.take<uint64_t>(ntiles + 1);
-    uint32_t *tcnt = w.take<uint32_t>(ntiles + 1);
-    uint64_t *ic = w.take<uint64_t>(ntiles + 1);
-    uint64_t *bits = w.take<uint64_t>(ntiles * 2 * ONW);
-    uint32_t *err = ctx->dev_status;
-    k_or_split<<<(unsigned)((ntiles + 1 + 15) / 16), 256, 0, ctx->stream>>>(A, B, na, nb, ntiles, split);
-    // write-pass workgroups per tile (sets.or_parts): 1/P of a tile's items, 4 per thread
-    const unsigned P = (unsigned)g_or_parts;
-    auto cnt = [&](size_t t0, uint32_t nt, hipStream_t s) {
-        if (g_or_count_dma) k_or_count_dma<OCB><<<nt, OCB, 0, s>>>(A, B, na, nb, split, tcnt, bits, t0);
-        else k_or_count<OCB><<<nt, OCB, 0, s>>>(A, B, na, nb, split, tcnt, bits, t0);
-    };
+    k_mp_split<M::kT, typename M::Le, typename M::Tiles>
+        <<<mp_split_grid(ntiles), 256, 0, ctx->stream>>>(A, na, nullptr, B, nb, nullptr, m.w.split);
+    auto cnt = [&](size_t t0, uint32_t nt, hipStream_t s) { M::count(m, t0, nt, s); };
     auto scn = [&](size_t t0, uint32_t nt, uint64_t *c, hipStream_t s) {
-        k_chunk_scan<<<1, 1024, 0, s>>>(tcnt, t0, nt, ic, c);
+        k_chunk_scan<<<1, 1024, 0, s>>>(m.w.tcnt, t0, nt, m.w.ic, c);
     };
-    auto wr = [&](size_t t0, uint32_t nt, hipStream_t s) {
-        const unsigned g = P * nt;
-        if (src) {
-            if (P == 2) k_or_write_src<1024, 256><<<g, 256, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
-            else if (P == 4) k_or_write_src<512, 128><<<g, 128, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
-            else k_or_write_src<2048, 512><<<g, 512, 0, s>>>(A, B, na, nb, split, bits, ic, O, src, t0, err);
-            return;
-        }
-        if (P == 2) k_or_write<1024, 256><<<g, 256, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
-        else if (P == 4) k_or_write<512, 128><<<g, 128, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
-        else k_or_write<2048, 512><<<g, 512, 0, s>>>(A, B, na, nb, split, bits, ic, O, t0, err);
-    };
-    return two_pass(ctx, ntiles, out_count, cnt, scn, wr, (size_t)g_or_chunk, take_fail_zero_bits(), bits,
-                    ntiles * 2 * ONW * 8);
+    auto wr = [&](size_t t0, uint32_t nt, hipStream_t s) { M::write(m, t0, nt, s); };
+    return two_pass(ctx, ntiles, out_count, cnt, scn, wr, M::chunk(), take_fail_zero_bits(), m.w.bits,
+                    ntiles * 2 * M::kNW * 8);
 }
 
 // ---------------------------------------------------------------- stable merge (no dedup)
@@ -749,7 +599,7 @@ static int orset_merge_twopass(crdt_ctx *ctx, const crdt_tuples &A, size_t na, c
 // copies first) -- the rank-order merge of the runs a key-range owner
 // receives in crdt_shard_*_merge_local.  Its length is na + nb, known on the
 // host, so a tree of these merges needs no read-back between levels.  Tiles
-// of OT merge items from k_or_split; per tile both runs staged in LDS, every
+// of OT merge items from k_mp_split; per tile both runs staged in LDS, every
 // item's output position = its index in its run + its rank in the other run
 // (B elements strictly below an A tag, A elements at or below a B tag).
 template <int NT>
@@ -763,7 +613,7 @@ __device__ __forceinline__ void tmerge_tile(const crdt_tuples &A, const crdt_tup
     // -- every item binary-searched its rank in the other run, ~11 dependent
     // 3-field LDS compares per item -- ran at ~1.6 TB/s.)
     constexpr int NI = OT / NT;
-    const LwwTile b = or_tile(split, t, na + nb);
+    const MergeTile b = merge_tile<OT>(split, t, na + nb);
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
         const uint32_t x = threadIdx.x + (uint32_t)j * NT;
@@ -857,13 +707,18 @@ __device__ __forceinline__ uint32_t batch_pair(const MergeBatch &mb, uint64_t x,
     return p;
 }
 
-__global__ __launch_bounds__(256) void k_or_split_batch(MergeBatch mb, uint64_t *__restrict__ split) {
-    const uint64_t e = ((((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6) << 2) + (uint64_t)((threadIdx.x & 63) >> 4);
+__global__ __launch_bounds__(256) void k_or_split_batch(MergeBatch mb, uint64_t *__restrict__ splits) {
+    constexpr int T = OT;
+    using Le = TupleLe<false>;
+    const int lane = threadIdx.x & 63, grp = lane >> 4, gl = lane & 15;
+    const uint64_t e = ((((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6) << 2) + (uint64_t)grp;
     const uint32_t p = batch_pair(mb, e, 1);
-    const uint64_t s0 = (uint64_t)mb.tile0[p] + p, nt = mb.tile0[p + 1] - mb.tile0[p];
-    // entries past the last pair's (nt + 1) compute nothing: t > ntiles
-    const uint64_t t = e - s0;
-    or_split_diag(mb.A[p], mb.B[p], mb.na[p], mb.nb[p], nt, t, split + s0);
+    const uint64_t s0 = (uint64_t)mb.tile0[p] + p, ntiles = mb.tile0[p + 1] - mb.tile0[p];
+    // entries past the last pair's (ntiles + 1) compute nothing: t > ntiles
+    const uint64_t t = e - s0, na = mb.na[p], nb = mb.nb[p];
+    const crdt_tuples &A = mb.A[p], &B = mb.B[p];
+    uint64_t *const split = splits + s0;
+#include "settile_split.inc"
 }
 
 template <int NT>
@@ -922,7 +777,8 @@ int tuples_merge_stable(crdt_ctx *ctx, const crdt_tuples &A, size_t na, const cr
     uint64_t *split = w.take<uint64_t>(ntiles + 1);
     const crdt_tuples empty{nullptr, nullptr, nullptr, nullptr};
     const crdt_tuples &a = na ? A : empty, &b = nb ? B : empty;
-    k_or_split<<<(unsigned)((ntiles + 1 + 15) / 16), 256, 0, ctx->stream>>>(a, b, na, nb, ntiles, split);
+    k_mp_split<OT, TupleLe<false>, PlainTiles>
+        <<<mp_split_grid(ntiles), 256, 0, ctx->stream>>>(a, na, nullptr, b, nb, nullptr, split);
     k_tmerge<512><<<(unsigned)ntiles, 512, 0, ctx->stream>>>(a, b, na, nb, split, O);
     return check_launch(ctx);
 }
@@ -935,39 +791,25 @@ __global__ void k_count_unsorted(crdt_tuples T, size_t n, unsigned long long *ba
     if (c) atomicAdd(bad, c);
 }
 
-static bool tuples_ok(const crdt_tuples *t) { return t && t->key && t->ts && t->rep && t->tomb; }
-
-// The write passes stage every field by LDS-DMA from element offsets: key /
-// ts / rep must be naturally aligned (any element offset of an allocation is).
-static bool dma_aligned(const crdt_tuples &t) {
-    return !((((uintptr_t)t.key | (uintptr_t)t.ts) & 7) | ((uintptr_t)t.rep & 3));
-}
-
-static bool bytes_overlap(const void *a, size_t an, const void *b, size_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return an && bn && x < y + bn && y < x + an;
-}
-// p[0 .. bytes) against the four columns of n tuples
-static bool overlaps_tuples(const void *p, size_t bytes, const crdt_tuples &t, size_t n) {
-    return bytes_overlap(p, bytes, t.key, n * 8) || bytes_overlap(p, bytes, t.ts, n * 8) ||
-           bytes_overlap(p, bytes, t.rep, n * 4) || bytes_overlap(p, bytes, t.tomb, n);
-}
-
-// WITH_SRC: the _src entry points (src_out: na + nb int64, the source index of every output)
+// WITH_SRC: the _src entry points (src_out: na + nb int64, the source index of every output).
+// A side of no elements may be a null pointer; the checks are settile.hpp's.
+// (The passes stage every field by LDS-DMA from element offsets: key / ts /
+// rep must be naturally aligned, as any element offset of an allocation is.)
 template <bool LWW, bool WITH_SRC = false>
 static int set_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_tuples *b, size_t nb,
                      crdt_tuples *out, uint64_t *out_count, int64_t *src_out = nullptr) {
     int rc = bind(ctx);
     if (rc) return rc;
-    if (!out_count || !tuples_ok(out)) return CRDT_E_INVAL;
-    if ((na && !tuples_ok(a)) || (nb && !tuples_ok(b))) return CRDT_E_INVAL;
-    if ((na && !dma_aligned(*a)) || (nb && !dma_aligned(*b))) return CRDT_E_INVAL;
+    if (!out_count || !out || tuples_null(out)) return CRDT_E_INVAL;
+    if ((na && (!a || tuples_null(a))) || (nb && (!b || tuples_null(b)))) return CRDT_E_INVAL;
+    if ((na && tuples_misaligned(a)) || (nb && tuples_misaligned(b))) return CRDT_E_INVAL;
     if (WITH_SRC && na + nb) {
         if (na + nb >= (1ULL << 62)) return CRDT_E_RANGE;
         const size_t sb = (na + nb) * 8;
         if (!src_out || ((uintptr_t)src_out & 7)) return CRDT_E_INVAL;
-        if ((na && overlaps_tuples(src_out, sb, *a, na)) || (nb && overlaps_tuples(src_out, sb, *b, nb)) ||
-            overlaps_tuples(src_out, sb, *out, na + nb))
+        // (every pointer compared here is non-null: spans_overlap's null rule never applies)
+        if ((na && tuples_overlap(a, na, src_out, sb)) || (nb && tuples_overlap(b, nb, src_out, sb)) ||
+            tuples_overlap(out, na + nb, src_out, sb))
             return CRDT_E_INVAL;
     }
     if (na + nb == 0) {
@@ -978,8 +820,8 @@ static int set_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na, const crdt_
     const crdt_tuples &A = na ? *a : empty;
     const crdt_tuples &B = nb ? *b : empty;
     int64_t *src = WITH_SRC ? src_out : nullptr;
-    return LWW ? lww_merge_keyruns(ctx, A, na, B, nb, *out, src, out_count)
-               : orset_merge_twopass(ctx, A, na, B, nb, *out, src, out_count);
+    return LWW ? merge_two_pass<LwwMode>(ctx, A, na, B, nb, *out, src, out_count)
+               : merge_two_pass<OrMode>(ctx, A, na, B, nb, *out, src, out_count);
 }
 
 // out_col[i] = the element src[i] names -- a_col[src[i]] (src[i] >= 0) or
@@ -1049,8 +891,9 @@ extern "C" int crdt_src_gather(crdt_ctx *ctx, const int64_t *src_dev, size_t n_m
         return CRDT_E_INVAL;
     if (mul_overflows(n_max, es)) return CRDT_E_RANGE;
     const size_t ob = n_max * es;
-    if (bytes_overlap(out_col_dev, ob, src_dev, n_max * 8) || bytes_overlap(out_col_dev, ob, a_col_dev, na * es) ||
-        bytes_overlap(out_col_dev, ob, b_col_dev, nb * es))
+    // (a null side has no elements: it met nothing before spans_overlap's null rule, too)
+    if (spans_overlap(out_col_dev, ob, src_dev, n_max * 8) || spans_overlap(out_col_dev, ob, a_col_dev, na * es) ||
+        spans_overlap(out_col_dev, ob, b_col_dev, nb * es))
         return CRDT_E_INVAL;
     const unsigned g = grid_for(n_max, 256, (unsigned)ctx->num_cus * 8);
     const hipStream_t s = ctx->stream;
@@ -1073,7 +916,8 @@ extern "C" int crdt_tuples_merge(crdt_ctx *ctx, const crdt_tuples *a, size_t na,
                                  const crdt_tuples *out) {
     int rc = bind(ctx);
     if (rc) return rc;
-    if ((na + nb && !tuples_ok(out)) || (na && !tuples_ok(a)) || (nb && !tuples_ok(b))) return CRDT_E_INVAL;
+    if ((na + nb && (!out || tuples_null(out))) || (na && (!a || tuples_null(a))) || (nb && (!b || tuples_null(b))))
+        return CRDT_E_INVAL;
     const crdt_tuples empty{nullptr, nullptr, nullptr, nullptr};
     return tuples_merge_stable(ctx, na ? *a : empty, na, nb ? *b : empty, nb, na + nb ? *out : empty);
 }
@@ -1085,7 +929,7 @@ extern "C" int crdt_tuples_count_unsorted(crdt_ctx *ctx, const crdt_tuples *t, s
     hipError_t e = hipMemsetAsync(bad, 0, sizeof(uint64_t), ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e);
     if (n < 2) return CRDT_OK;
-    if (!tuples_ok(t)) return CRDT_E_INVAL;
+    if (!t || tuples_null(t)) return CRDT_E_INVAL;
     k_count_unsorted<<<grid_for(n, 256, (unsigned)ctx->num_cus * 8), 256, 0, ctx->stream>>>(
         *t, n, (unsigned long long *)bad);
     return check_launch(ctx);

@@ -16,7 +16,7 @@
     __shared__ alignas(16) uint8_t s_tomb[CAP + 64];
     const uint64_t t = t0 + blockIdx.x / P;
     const uint32_t h = blockIdx.x % P;
-    const LwwTile b = lww_tile(split, t, na + nb);
+    const MergeTile b = merge_tile<LT>(split, t, na + nb);
     const int lane = threadIdx.x & 63;
     const uint64_t word_a = bits[t * 2 * LNW + lane], word_e = bits[t * 2 * LNW + LNW + lane];
     const uint64_t ob = ic[t];                           // (with the split and bitmaps: no load after the barrier)

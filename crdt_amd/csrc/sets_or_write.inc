@@ -14,7 +14,7 @@
     __shared__ alignas(16) uint8_t s_tomb[CAP + 64];
     const uint64_t t = t0 + blockIdx.x / P;
     const uint32_t h = blockIdx.x % P;
-    const LwwTile b = or_tile(split, t, na + nb);
+    const MergeTile b = merge_tile<OT>(split, t, na + nb);
     const int lane = threadIdx.x & 63;
     const bool wl_ok = lane < ONW;
     // split, bitmap words and offset loads issued together (none after the barrier)

@@ -1,5 +1,8 @@
 // settile.hpp -- the tile scaffold of the set-state ops (setread, setdelta,
-// setcompact, setdigest, setcausal, setapply .hip).  Every one of them
+// setcompact, setdigest, setcausal, setapply .hip) and of the
+// set merges it was first copied from (sets.hip: the argument checks, the
+// workspace and the split; LWW tiles there are 4096 items and the scan is
+// k_chunk_scan, over chunks of tiles).  Every one of them
 // is count / scan / write over tiles of 2048 items with one workspace shape:
 //   tcnt[t]  the tile's output count (under an empty carry)
 //   rec[t]   the tile's carry record (ops whose decisions cross tiles)
@@ -247,8 +250,8 @@ struct TupleLe {
 };
 
 // split[t] = a elements among the first min(t T, n) merged items, t = 0 ..
-// tiles: one 16-lane group per diagonal, four per wave (the 16-ary search of
-// k_or_split / k_lww_split, the lengths read on the device).
+// tiles: one 16-lane group per diagonal, four per wave, each a 16-ary search
+// (settile_split.inc), the lengths read on the device.
 template <int T, class Le, class Tiles>
 __global__ __launch_bounds__(256) void k_mp_split(crdt_tuples A, uint64_t na_max, const uint64_t *__restrict__ na_dev,
                                                   crdt_tuples B, uint64_t nb_max, const uint64_t *__restrict__ nb_dev,
@@ -259,33 +262,7 @@ __global__ __launch_bounds__(256) void k_mp_split(crdt_tuples A, uint64_t na_max
     if (ntiles == 0) return;
     const int lane = threadIdx.x & 63, grp = lane >> 4, gl = lane & 15;
     const uint64_t t = ((((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6) << 2) + (uint64_t)grp;
-    const uint64_t n = na + nb;
-    const uint64_t d = t < ntiles ? t * T : n;
-    uint64_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
-    bool done = t > ntiles || hi <= lo;
-    // P(i) = A[i] <= B[d-1-i]: true below the split, false from it
-    while (__ballot(!done)) {
-        const uint64_t span = hi - lo;
-        const bool small = span <= 16;
-        const uint64_t c = small ? lo + (uint64_t)gl : lo + ((uint64_t)gl * span) / 16;
-        const bool valid = !done && (small ? (uint64_t)gl < span : true);
-        const bool p = valid && Le::le(A, c, B, d - 1 - c);
-        const unsigned m = (unsigned)((__ballot(p) >> (grp * 16)) & 0xFFFF);
-        const unsigned cnt = (unsigned)__popc(m);
-        if (!done) {
-            if (small) {
-                lo += cnt;
-                done = true;
-            } else {
-                const uint64_t nlo = cnt > 0 ? lo + (((uint64_t)(cnt - 1)) * span) / 16 + 1 : lo;
-                const uint64_t nhi = cnt < 16 ? lo + ((uint64_t)cnt * span) / 16 : hi;
-                lo = nlo;
-                hi = nhi;
-                done = hi <= lo;
-            }
-        }
-    }
-    if (gl == 0 && t <= ntiles) split[t] = lo;
+#include "settile_split.inc"
 }
 inline unsigned mp_split_grid(size_t ntiles) { return (unsigned)((ntiles + 1 + 15) / 16); }   // 16 diagonals per workgroup
 

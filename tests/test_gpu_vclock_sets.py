@@ -250,3 +250,32 @@ def test_orset_write_parts(eng, parts):
         test_sets_unaligned_views(eng, 13, 11)
     finally:
         set_knob(b"sets.or_parts", 2)
+
+
+@pytest.mark.diag
+def test_orset_count_register_staging(eng):
+    """The OR-Set count pass with its tile staged through registers
+    (sets.or_count_dma = 0; LDS-DMA is the default): tile edges, a side that is
+    empty (no element before the tile on it), equal tags across a tile edge,
+    identical inputs, an unaligned view; == the oracle."""
+    set_knob(b"sets.or_count_dma", 0)
+    try:
+        for na, nb in ((2047, 1), (2048, 2048), (0, 3000), (3000, 0)):
+            _check(eng, *_sets(96 + na, na, nb, max(1, (na + nb) // 3)))
+        test_sets_long_runs_cross_tiles(eng)
+        test_sets_identical_inputs_idempotent(eng)
+        test_sets_unaligned_views(eng, 3, 5)
+        assert eng.device_status(clear=True) == 0
+    finally:
+        set_knob(b"sets.or_count_dma", 1)
+
+
+@pytest.mark.diag
+def test_lww_split_key_run_longer_than_tile(eng):
+    """The keys-only merge-path split where one key's run is longer than a
+    4096-item LWW tile on both sides, so whole tiles and their diagonals lie
+    inside one key: 40 000 tuples a side over 4 keys (runs of ~10 000), and
+    over 100 keys (runs of ~400: many keys per tile); == the oracle."""
+    _check(eng, *_sets(97, 40_000, 40_000, 4))
+    _check(eng, *_sets(97, 40_000, 40_000, 100))
+    assert eng.device_status(clear=True) == 0
