@@ -200,6 +200,8 @@ SIGNATURES = {
     "crdt_tuples_count_unsorted": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, _P]),
     "crdt_set_elements": (_I, [_CTX, _I, C.POINTER(crdt_tuples), _SZ, _P, _P, _P]),
     "crdt_u64_contains": (_I, [_CTX, _P, _SZ, _P, _P, _SZ, _P]),
+    "crdt_map_read": (_I, [_CTX, _I, C.POINTER(crdt_tuples), _SZ, _P, _P, _P, _P, _P]),
+    "crdt_map_lookup": (_I, [_CTX, _I, C.POINTER(crdt_tuples), _SZ, _P, _P, _SZ, _P, _P]),
     "crdt_set_delta": (_I, [_CTX, _I, C.POINTER(crdt_tuples), _SZ, _P, C.POINTER(crdt_tuples), _SZ, _P,
                             C.POINTER(crdt_tuples), _P]),
     "crdt_set_compact": (_I, [_CTX, _I, C.POINTER(crdt_tuples), _SZ, _P, _P, _SZ, C.POINTER(crdt_tuples), _P, _P]),

@@ -541,6 +541,98 @@ class Engine:
         out, src, count = self.set_compact(t, lww, cut, with_src=True)
         return out, self.gather_src(src, val, val[:0], n_dev=count), count
 
+    # -- map reads: each member key's winning tuple, sibling count, point lookup (crdt_map_read / crdt_map_lookup)
+    def map_read(self, t: TupleSet, lww: bool, n_dev: torch.Tensor | None = None, with_keys: bool = True,
+                 with_nsib: bool = False, keys: torch.Tensor | None = None, win: torch.Tensor | None = None,
+                 nsib: torch.Tensor | None = None, count: torch.Tensor | None = None):
+        """One row per member key of the sorted set state ``t`` (the keys of
+        :meth:`set_elements`, ascending): returns (keys, win, nsib, count),
+        device tensors of capacity len(t) whose first ``count`` rows are
+        valid, no synchronisation.  win[i] (int64) is the index in t of the
+        first copy of key i's winner tag -- LWW: the key's maximal tag;
+        OR-Set (also a causal-form state): the greatest live tag -- for
+        :meth:`gather_src`; nsib[i] (int32 storage of uint32) the number of
+        distinct live tags of the key (LWW: 1), > 1 where concurrent puts left
+        the key multi-valued.  keys / nsib are None unless asked for
+        (``with_keys`` / ``with_nsib``, or a tensor to write into).  ``n_dev``
+        as in :meth:`set_elements`."""
+        n = len(t)
+        dev = self.device
+        if keys is None and with_keys:
+            keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        if nsib is None and with_nsib:
+            nsib = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        win = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if win is None else win
+        count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+        self._check_tuples(t)
+        self._check(win, count, itemsize=8)
+        if win.dtype != torch.int64 or win.numel() < n:
+            raise ValueError("map_read: win must be int64 and hold len(t) rows")
+        if keys is not None:
+            self._check(keys, itemsize=8)
+        if nsib is not None:
+            self._check(nsib, itemsize=4)
+        if (keys is not None and keys.numel() < n) or (nsib is not None and nsib.numel() < n):
+            raise ValueError("map_read: keys / nsib hold fewer rows than t has tuples")
+        if n_dev is not None:
+            self._check(n_dev, itemsize=8)
+        ct = t.c()
+        self._call("crdt_map_read", 0 if lww else 1, C.byref(ct), n, _ptr(n_dev), _ptr(keys), _ptr(win), _ptr(nsib),
+                   count.data_ptr())
+        return keys, win, nsib, count
+
+    def map_values(self, t: TupleSet, val: torch.Tensor, lww: bool, n_dev: torch.Tensor | None = None):
+        """The map a state holds beside its value column (val[i] belongs to
+        t's tuple i): returns (keys, values, count), device-resident -- the
+        member keys ascending and each key's winning value: the read, then
+        one :meth:`gather_src` chained off its device count, no read-back."""
+        if val.shape[0] != len(t):
+            raise ValueError("map_values: one value per tuple")
+        keys, win, _, count = self.map_read(t, lww, n_dev=n_dev)
+        return keys, self.gather_src(win, val, val[:0], n_dev=count), count
+
+    def map_lookup(self, t: TupleSet, probes: torch.Tensor, lww: bool, n_dev: torch.Tensor | None = None,
+                   with_nsib: bool = False, win: torch.Tensor | None = None, nsib: torch.Tensor | None = None):
+        """:meth:`map_read`'s row of each probe key (uint64 in int64 storage,
+        any order, duplicates allowed): returns (win, nsib), device tensors
+        of len(probes), no synchronisation -- win[i] = -1 and nsib[i] = 0 for
+        a key that is not a member; nsib is None unless asked for."""
+        m = probes.numel()
+        win = torch.empty(max(m, 1), dtype=torch.int64, device=self.device)[:m] if win is None else win
+        if nsib is None and with_nsib:
+            nsib = torch.empty(max(m, 1), dtype=torch.int32, device=self.device)[:m]
+        self._check_tuples(t)
+        self._check(probes, win, itemsize=8)
+        if win.dtype != torch.int64 or win.numel() < m:
+            raise ValueError("map_lookup: win must be int64 and hold one entry per probe")
+        if nsib is not None:
+            self._check(nsib, itemsize=4)
+            if nsib.numel() < m:
+                raise ValueError("map_lookup: nsib holds fewer entries than there are probes")
+        if n_dev is not None:
+            self._check(n_dev, itemsize=8)
+        ct = t.c()
+        self._call("crdt_map_lookup", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev), _ptr(probes), m, _ptr(win),
+                   _ptr(nsib))
+        return win, nsib
+
+    def map_get(self, t: TupleSet, val: torch.Tensor, probes: torch.Tensor, default, lww: bool,
+                n_dev: torch.Tensor | None = None) -> torch.Tensor:
+        """The value of each probe key, ``default`` where the key is not a
+        member: the lookup, then one :meth:`gather_src` whose b side is the
+        one-element default column (a lookup's -1 names its element 0), no
+        synchronisation.  ``default``: a scalar, or a tensor of one element /
+        row of val's dtype."""
+        if val.shape[0] != len(t):
+            raise ValueError("map_get: one value per tuple")
+        if torch.is_tensor(default):
+            dflt = default.to(device=self.device, dtype=val.dtype).reshape((1,) + tuple(val.shape[1:])).contiguous()
+        else:
+            dflt = torch.full((1,) + tuple(val.shape[1:]), default, dtype=val.dtype, device=self.device)
+        win, _ = self.map_lookup(t, probes, lww, n_dev=n_dev)
+        out = self.gather_src(win, val, dflt)
+        return out[:probes.numel()]
+
     # -- the tombstone-free OR-Set: causal merge under version vectors (crdt_orset_merge_causal)
     def causal_merge(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet, ctx_b: torch.Tensor | None,
                      n_a_dev: torch.Tensor | None = None, n_b_dev: torch.Tensor | None = None,

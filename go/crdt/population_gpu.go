@@ -184,6 +184,42 @@ func KeysContain(keysDev *C.uint64_t, nMax int, nDev, probesDev *C.uint64_t, m i
 	return status(C.crdt_u64_contains(gpuCtx, keysDev, C.size_t(nMax), nDev, probesDev, C.size_t(m), outDev))
 }
 
+// MapRead: the map a sorted set state holds beside a value column -- one row
+// per member key (SetElements' keys, ascending): the key into keysOutDev (may
+// be nil), the index in t of the first copy of the key's winner tag into
+// winOutDev (LWW: the maximal tag; OR-Set: the greatest live tag) and the
+// number of distinct live tags into nsibOutDev (may be nil; LWW: 1; > 1: the
+// key is multi-valued), each of capacity nMax rows; their number into
+// countDev.  winOutDev is SrcGather's a-side encoding: gather the value column
+// by it with countDev as the device length.  Enqueued: crdt_ctx_sync before
+// reading.
+func MapRead(lww bool, t *C.crdt_tuples, nMax int, nDev, keysOutDev *C.uint64_t, winOutDev *C.int64_t,
+	nsibOutDev *C.uint32_t, countDev *C.uint64_t) error {
+	mode := C.int(C.CRDT_SET_ORSET)
+	if lww {
+		mode = C.int(C.CRDT_SET_LWW)
+	}
+	return status(C.crdt_map_read(gpuCtx, mode, t, C.size_t(nMax), nDev, keysOutDev, winOutDev, nsibOutDev, countDev))
+}
+
+// MapLookup: MapRead's row of each of the m probe keys in probesDev (any
+// order, duplicates allowed): winOutDev[i] = the win of probesDev[i], or -1
+// when the key is not a member; nsibOutDev (may be nil) its sibling count, 0
+// for a non-member.  To SrcGather -1 is element 0 of the b side: a one-element
+// b column is the default of the missing keys.  No probes (m == 0, the device
+// pointers may then be nil) enqueue nothing.
+func MapLookup(lww bool, t *C.crdt_tuples, nMax int, nDev, probesDev *C.uint64_t, m int, winOutDev *C.int64_t,
+	nsibOutDev *C.uint32_t) error {
+	if m == 0 {
+		return nil
+	}
+	mode := C.int(C.CRDT_SET_ORSET)
+	if lww {
+		mode = C.int(C.CRDT_SET_LWW)
+	}
+	return status(C.crdt_map_lookup(gpuCtx, mode, t, C.size_t(nMax), nDev, probesDev, C.size_t(m), winOutDev, nsibOutDev))
+}
+
 // SetDelta: the tuples of the sorted set state src that dst lacks -- the
 // smallest D with merge(dst, D) == merge(dst, src), dst the tie-winning side --
 // in ascending order into out (capacity nsMax tuples), their number into

@@ -318,6 +318,54 @@ int crdt_set_elements(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_ma
  * count_dev as n_dev.  Stream-ordered, no host synchronisation. */
 int crdt_u64_contains(crdt_ctx *ctx, const uint64_t *sorted_dev, size_t n_max, const uint64_t *n_dev,
                       const uint64_t *probes_dev, size_t m, uint8_t *out_dev);
+/* ---- map reads: the key -> value view of a set state that keeps a value
+ * column beside its tuples (what the reference serves: CurrentState on GET
+ * /data, main.go:129-139).  t[0 .. n) sorted ascending by (key, ts, rep),
+ * copies of one tag in any order and number; n from n_max / n_dev exactly as
+ * in crdt_set_elements; mode CRDT_SET_LWW or CRDT_SET_ORSET (a causal-form
+ * state, whose tombs are all 0, is read with CRDT_SET_ORSET).
+ *   member keys : exactly those of crdt_set_elements(mode, t), ascending, one
+ *                 row each.
+ *   winner      : OR-Set -- the greatest (ts, rep) live tag of the key; a tag
+ *                 is live iff none of its copies is tombstoned.  LWW -- the
+ *                 key's maximal tag; the key is a member iff the tomb of that
+ *                 tag's first copy is 0.
+ *   win (int64) : the index in t of the first copy of the winner tag: the
+ *                 a-side encoding of crdt_src_gather, so
+ *                 crdt_src_gather(win, n_max, count_dev, val, n, NULL, 0,
+ *                 out_val, elem) yields the map's values with no read-back.
+ *   nsib (u32)  : OR-Set -- the number of distinct live tags of the key, at
+ *                 least 1, saturating at 2^32 - 1; LWW -- 1.  nsib > 1 marks a
+ *                 key that concurrent puts left multi-valued.
+ * crdt_map_read writes one row per member key, in ascending key order, and
+ * their number to *count_dev (device uint64).  keys_out_dev and nsib_out_dev
+ * may each be NULL (a NULL nsib_out_dev costs nothing: the sibling walk is
+ * compiled out); win_out_dev is required when n_max > 0.  Each output holds at
+ * least n_max rows, is naturally aligned, and overlaps neither t nor another
+ * output.  *n_dev > n_max: no tuple is touched, nothing is written to the
+ * outputs, *count_dev = ~0 and CRDT_DEV_RANGE is raised.  No kernel reads a
+ * tuple at or past min(*n_dev, n_max) or before 0.  Stream-ordered, no host
+ * synchronisation (capturable after crdt_ctx_reserve).  CRDT_E_INVAL: NULL ctx
+ * / t / count_dev, bad mode, NULL fields of t or a NULL win_out_dev with n_max
+ * > 0, misalignment, overlap; CRDT_E_RANGE: n_max >= 2^62 or more tiles than a
+ * launch holds.  n_max == 0 launches nothing but the count store. */
+int crdt_map_read(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
+                  uint64_t *keys_out_dev, int64_t *win_out_dev, uint32_t *nsib_out_dev, uint64_t *count_dev);
+/* Point lookup against the same state: m probe keys in any order, duplicates
+ * allowed.  win_out_dev[i] = the win crdt_map_read gives probes_dev[i], or -1
+ * if the key is not a member; nsib_out_dev (may be NULL) its nsib, 0 for a
+ * non-member.  To crdt_src_gather -1 is element 0 of the b side, so a gather
+ * by win_out_dev with a one-element b_col writes a caller-chosen default for
+ * the missing keys and raises nothing.  *n_dev > n_max: every win_out is -1,
+ * every nsib_out 0, and CRDT_DEV_RANGE is raised (as crdt_u64_contains).  One
+ * thread per probe: a binary search on t.key clamped to the length, then the
+ * key's tags from its run's end; no workspace, no synchronisation; m == 0
+ * launches nothing.  CRDT_E_INVAL: NULL ctx / t, bad mode, and with m > 0 a
+ * NULL probes_dev / win_out_dev, NULL fields of t with n_max > 0,
+ * misalignment, an output overlapping t, probes_dev or the other output;
+ * CRDT_E_RANGE: n_max >= 2^62 or m >= 2^60. */
+int crdt_map_lookup(crdt_ctx *ctx, int mode, const crdt_tuples *t, size_t n_max, const uint64_t *n_dev,
+                    const uint64_t *probes_dev, size_t m, int64_t *win_out_dev, uint32_t *nsib_out_dev);
 /* ---- set deltas: the tuples of one set state that another lacks (the
  * reference's gossip pull ships the entire Diff every round, main.go:153-170
  * and :245-256).  delta(src, dst) = the smallest set of tuples D with
