@@ -37,6 +37,11 @@ def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def _ref(s: "TupleSet | None"):
+    """The by-reference crdt_tuples argument naming ``s``; None (an absent optional output) stays None."""
+    return None if s is None else C.byref(s.c())
+
+
 @dataclass
 class TupleSet:
     """SoA (key u64, ts u64, rep u32, tomb u8) tuples, sorted by (key, ts, rep)."""
@@ -118,14 +123,64 @@ class Engine:
         self._bind()
         call(fn, self.ctx, *args, ctx=self.ctx)
 
-    def _check(self, *ts: torch.Tensor, itemsize: int | None = None) -> None:
+    def _check(self, *ts: torch.Tensor | None, itemsize: int | None = None) -> None:
+        """Refuse a tensor the library cannot take; None, an absent optional, passes."""
         for t in ts:
+            if t is None:
+                continue
             if t.device != self.device:
                 raise ValueError(f"tensor on {t.device}, engine on {self.device}")
             if not t.is_contiguous():
                 raise ValueError("tensors must be contiguous")
             if itemsize is not None and t.element_size() != itemsize:
                 raise ValueError(f"expected {itemsize}-byte elements, got {t.dtype}")
+
+    def _check_tuples(self, *sets: TupleSet | None) -> None:
+        dev = self.device
+        for s in sets:
+            if s is None:
+                continue
+            key, ts, rep, tomb = s.key, s.ts, s.rep, s.tomb
+            # one pass accepts well-formed fields; anything else gets _check's refusal, in field order
+            if not (key.device == dev and key.is_contiguous() and key.element_size() == 8
+                    and ts.device == dev and ts.is_contiguous() and ts.element_size() == 8
+                    and rep.device == dev and rep.is_contiguous() and rep.element_size() == 4
+                    and tomb.device == dev and tomb.is_contiguous() and tomb.element_size() == 1):
+                self._check(s.key, s.ts, itemsize=8)
+                self._check(s.rep, itemsize=4)
+                self._check(s.tomb, itemsize=1)
+
+    # -- what the set-state wrappers share: the buffers a call writes, allocated
+    #    where not given and checked where given, and what it hands back
+    def _count(self, count: torch.Tensor | None) -> torch.Tensor:
+        return torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+
+    def _out_tuples(self, out: TupleSet | None, n: int, short: str) -> TupleSet:
+        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
+        if len(out) < n:
+            raise ValueError(short)
+        return out
+
+    def _out_src(self, src: torch.Tensor | None, with_src: bool, n: int, bad: str) -> torch.Tensor | None:
+        if src is None and with_src:
+            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        if src is not None:
+            self._check(src, itemsize=8)
+            if src.dtype != torch.int64 or src.numel() < n:
+                raise ValueError(bad)
+        return src
+
+    def _trimmed(self, count: torch.Tensor) -> int:
+        """The count read back, once the device status is checked: ``trim``'s one synchronisation."""
+        self.check_device()
+        return int(count.item())
+
+    def _result(self, trim: bool, count: torch.Tensor, out: TupleSet, src: torch.Tensor | None, *extras):
+        """(out[, src], *extras, count), out / src cut to the count with ``trim``."""
+        if trim:
+            k = self._trimmed(count)
+            out, src = out.slice(k), None if src is None else src[:k]
+        return (out, *extras, count) if src is None else (out, src, *extras, count)
 
     def sync(self) -> None:
         self._call("crdt_ctx_sync")
@@ -224,17 +279,11 @@ class Engine:
                    count: torch.Tensor | None, trim: bool):
         na, nb = len(a), len(b)
         out = TupleSet.empty(max(na + nb, 1), self.device) if out is None else out
-        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
-        for s in (a, b, out):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        ca, cb, co = a.c(), b.c(), out.c()
-        self._call(fn, C.byref(ca), na, C.byref(cb), nb, C.byref(co), count.data_ptr())
-        if trim:                              # synchronises anyway: check the look-back's flag too
-            self.check_device()
-            return out.slice(int(count.item()))
-        return out, count
+        count = self._count(count)
+        self._check_tuples(a, b, out)
+        self._call(fn, _ref(a), na, _ref(b), nb, _ref(out), count.data_ptr())
+        # trim synchronises anyway: check the look-back's flag too
+        return out.slice(self._trimmed(count)) if trim else (out, count)
 
     def lww_merge(self, a: TupleSet, b: TupleSet, out: TupleSet | None = None,
                   count: torch.Tensor | None = None, trim: bool = True):
@@ -250,18 +299,14 @@ class Engine:
     #    gather of value columns by it (crdt_*_merge_src / crdt_src_gather)
     def _set_merge_src(self, fn: str, a: TupleSet, b: TupleSet, out: TupleSet | None, src: torch.Tensor | None):
         na, nb = len(a), len(b)
+        short = "merge_src: out and src (int64) must hold len(a) + len(b) entries"
         out = TupleSet.empty(max(na + nb, 1), self.device) if out is None else out
-        src = torch.empty(max(na + nb, 1), dtype=torch.int64, device=self.device) if src is None else src
-        count = torch.empty(1, dtype=torch.int64, device=self.device)
-        for s in (a, b, out):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        self._check(src, itemsize=8)
-        if src.dtype != torch.int64 or src.numel() < na + nb or len(out) < na + nb:
-            raise ValueError("merge_src: out and src (int64) must hold len(a) + len(b) entries")
-        ca, cb, co = a.c(), b.c(), out.c()
-        self._call(fn, C.byref(ca), na, C.byref(cb), nb, C.byref(co), src.data_ptr(), count.data_ptr())
+        self._check_tuples(a, b, out)
+        src = self._out_src(src, True, na + nb, short)
+        if len(out) < na + nb:
+            raise ValueError(short)
+        count = self._count(None)
+        self._call(fn, _ref(a), na, _ref(b), nb, _ref(out), src.data_ptr(), count.data_ptr())
         return out, count, src
 
     def lww_merge_src(self, a: TupleSet, b: TupleSet, out: TupleSet | None = None, src: torch.Tensor | None = None):
@@ -305,8 +350,7 @@ class Engine:
             raise ValueError("gather_src: src must be a 1-D int64 tensor")
         if out.dtype != a_col.dtype or tuple(out.shape[1:]) != row or out.shape[0] < n:
             raise ValueError("gather_src: out must hold len(src) elements of the columns' dtype")
-        if n_dev is not None:
-            self._check(n_dev, itemsize=8)
+        self._check(n_dev, itemsize=8)
         self._call("crdt_src_gather", _ptr(src), n, _ptr(n_dev), _ptr(a_col), a_col.shape[0], _ptr(b_col),
                    b_col.shape[0], _ptr(out), es)
         return out
@@ -345,9 +389,8 @@ class Engine:
         (one synchronisation); reserves the workspace its planned calls use."""
         from ._lib import crdt_set_plan
         plan = crdt_set_plan()
-        ca, cb = a.c(), b.c()
-        self._call("crdt_set_merge_plan", 0 if lww else 1, C.byref(ca), len(a), C.byref(cb), len(b),
-                   1 if widen else 0, C.byref(plan))
+        self._call("crdt_set_merge_plan", 0 if lww else 1, _ref(a), len(a), _ref(b), len(b), 1 if widen else 0,
+                   C.byref(plan))
         return plan
 
     def merge_unsorted_planned(self, lww: bool, plan, a: TupleSet, b: TupleSet, out: TupleSet,
@@ -355,24 +398,16 @@ class Engine:
         """crdt_{lww,orset}_merge_unsorted_planned: the D2 merge enqueued with
         no host synchronisation (graph-capturable); *count = 2^64 - 1 and the
         CRDT_DEV_PLAN flag when the inputs left the plan."""
-        for s in (a, b, out):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        ca, cb, co = a.c(), b.c(), out.c()
+        self._check_tuples(a, b, out)
         fn = "crdt_lww_merge_unsorted_planned" if lww else "crdt_orset_merge_unsorted_planned"
-        self._call(fn, C.byref(plan), C.byref(ca), len(a), C.byref(cb), len(b), C.byref(co), count.data_ptr())
+        self._call(fn, C.byref(plan), _ref(a), len(a), _ref(b), len(b), _ref(out), count.data_ptr())
 
     def sort_tuples(self, t: TupleSet, out: TupleSet | None = None) -> TupleSet:
         """Device sort into ascending (key, ts, rep, tomb) order (config D2)."""
         n = len(t)
         out = TupleSet.empty(n, self.device) if out is None else out
-        for s in (t, out):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        ct, co = t.c(), out.c()
-        self._call("crdt_tuples_sort", C.byref(ct), n, C.byref(co))
+        self._check_tuples(t, out)
+        self._call("crdt_tuples_sort", _ref(t), n, _ref(out))
         return out
 
     def lower_bound_u64(self, sorted_u64: torch.Tensor, probes: torch.Tensor) -> torch.Tensor:
@@ -407,24 +442,17 @@ class Engine:
         return self._set_read(t, lww, n_dev, None, count)
 
     def _set_read(self, t: TupleSet, lww: bool, n_dev, out, count) -> torch.Tensor:
-        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
-        self._check(t.key, t.ts, count, itemsize=8)
-        self._check(t.rep, itemsize=4)
-        self._check(t.tomb, itemsize=1)
-        if n_dev is not None:
-            self._check(n_dev, itemsize=8)
-        ct = t.c()
-        self._call("crdt_set_elements", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev), _ptr(out),
-                   count.data_ptr())
+        count = self._count(count)
+        self._check_tuples(t)
+        self._check(count, n_dev, itemsize=8)
+        self._call("crdt_set_elements", 0 if lww else 1, _ref(t), len(t), _ptr(n_dev), _ptr(out), count.data_ptr())
         return count
 
     def keys_contain(self, sorted_keys: torch.Tensor, probes: torch.Tensor,
                      n_dev: torch.Tensor | None = None) -> torch.Tensor:
         """uint8[i] = 1 iff probes[i] is among the first n_dev (default: all)
         of the ascending uint64 ``sorted_keys`` (crdt_u64_contains)."""
-        self._check(sorted_keys, probes, itemsize=8)
-        if n_dev is not None:
-            self._check(n_dev, itemsize=8)
+        self._check(sorted_keys, probes, n_dev, itemsize=8)
         res = torch.empty(probes.numel(), dtype=torch.uint8, device=self.device)
         self._call("crdt_u64_contains", _ptr(sorted_keys), sorted_keys.numel(), _ptr(n_dev), _ptr(probes),
                    probes.numel(), _ptr(res))
@@ -442,14 +470,9 @@ class Engine:
         that side are read; a value over the side's length leaves count =
         2^64 - 1 and raises CRDT_DEV_RANGE in :meth:`device_status`.  With
         ``trim`` the device status is checked and the sliced D returned."""
-        out = TupleSet.empty(max(len(src), 1), self.device) if out is None else out
-        if len(out) < len(src):
-            raise ValueError("set_delta: out holds fewer tuples than src")
+        out = self._out_tuples(out, len(src), "set_delta: out holds fewer tuples than src")
         count = self._set_delta(src, dst, lww, n_src_dev, n_dst_dev, out, count)
-        if trim:
-            self.check_device()
-            return out.slice(int(count.item()))
-        return out, count
+        return out.slice(self._trimmed(count)) if trim else (out, count)
 
     def set_delta_count(self, src: TupleSet, dst: TupleSet, lww: bool, n_src_dev: torch.Tensor | None = None,
                         n_dst_dev: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
@@ -459,19 +482,12 @@ class Engine:
         return self._set_delta(src, dst, lww, n_src_dev, n_dst_dev, None, count)
 
     def _set_delta(self, src: TupleSet, dst: TupleSet, lww: bool, n_src_dev, n_dst_dev, out, count) -> torch.Tensor:
-        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        count = self._count(count)
         self._check(count, itemsize=8)
-        for s in (src, dst) + (() if out is None else (out,)):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        for n_dev in (n_src_dev, n_dst_dev):
-            if n_dev is not None:
-                self._check(n_dev, itemsize=8)
-        cs, cd = src.c(), dst.c()
-        co = None if out is None else out.c()
-        self._call("crdt_set_delta", 0 if lww else 1, C.byref(cs), len(src), _ptr(n_src_dev), C.byref(cd), len(dst),
-                   _ptr(n_dst_dev), None if co is None else C.byref(co), count.data_ptr())
+        self._check_tuples(src, dst, out)
+        self._check(n_src_dev, n_dst_dev, itemsize=8)
+        self._call("crdt_set_delta", 0 if lww else 1, _ref(src), len(src), _ptr(n_src_dev), _ref(dst), len(dst),
+                   _ptr(n_dst_dev), _ref(out), count.data_ptr())
         return count
 
     # -- tombstone compaction under a causal-stability cut (crdt_set_compact)
@@ -492,21 +508,10 @@ class Engine:
         :meth:`set_elements`; with ``trim`` the device status is checked and
         the sliced results returned."""
         n = len(t)
-        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
-        if len(out) < n:
-            raise ValueError("set_compact: out holds fewer tuples than t")
-        if src is None and with_src:
-            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
-        if src is not None:
-            self._check(src, itemsize=8)
-            if src.dtype != torch.int64 or src.numel() < n:
-                raise ValueError("set_compact: src must be int64 and hold len(t) entries")
+        out = self._out_tuples(out, n, "set_compact: out holds fewer tuples than t")
+        src = self._out_src(src, with_src, n, "set_compact: src must be int64 and hold len(t) entries")
         count = self._set_compact(t, lww, cut, n_dev, out, src, count)
-        if trim:
-            self.check_device()
-            k = int(count.item())
-            return (out.slice(k), count) if src is None else (out.slice(k), src[:k], count)
-        return (out, count) if src is None else (out, src, count)
+        return self._result(trim, count, out, src)
 
     def set_compact_count(self, t: TupleSet, lww: bool, cut: torch.Tensor | None, n_dev: torch.Tensor | None = None,
                           count: torch.Tensor | None = None) -> torch.Tensor:
@@ -515,20 +520,12 @@ class Engine:
         return self._set_compact(t, lww, cut, n_dev, None, None, count)
 
     def _set_compact(self, t: TupleSet, lww: bool, cut, n_dev, out, src, count) -> torch.Tensor:
-        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        count = self._count(count)
         self._check(count, itemsize=8)
-        for s in (t,) + (() if out is None else (out,)):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        for x in (cut, n_dev):
-            if x is not None:
-                self._check(x, itemsize=8)
-        ct = t.c()
-        co = None if out is None else out.c()
-        self._call("crdt_set_compact", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev), _ptr(cut),
-                   0 if cut is None else cut.numel(), None if co is None else C.byref(co), _ptr(src),
-                   count.data_ptr())
+        self._check_tuples(t, out)
+        self._check(cut, n_dev, itemsize=8)
+        self._call("crdt_set_compact", 0 if lww else 1, _ref(t), len(t), _ptr(n_dev), _ptr(cut),
+                   0 if cut is None else cut.numel(), _ref(out), _ptr(src), count.data_ptr())
         return count
 
     def map_compact(self, t: TupleSet, val: torch.Tensor, lww: bool, cut: torch.Tensor | None):
@@ -563,21 +560,17 @@ class Engine:
         if nsib is None and with_nsib:
             nsib = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         win = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if win is None else win
-        count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+        count = self._count(count)
         self._check_tuples(t)
         self._check(win, count, itemsize=8)
         if win.dtype != torch.int64 or win.numel() < n:
             raise ValueError("map_read: win must be int64 and hold len(t) rows")
-        if keys is not None:
-            self._check(keys, itemsize=8)
-        if nsib is not None:
-            self._check(nsib, itemsize=4)
+        self._check(keys, itemsize=8)
+        self._check(nsib, itemsize=4)
         if (keys is not None and keys.numel() < n) or (nsib is not None and nsib.numel() < n):
             raise ValueError("map_read: keys / nsib hold fewer rows than t has tuples")
-        if n_dev is not None:
-            self._check(n_dev, itemsize=8)
-        ct = t.c()
-        self._call("crdt_map_read", 0 if lww else 1, C.byref(ct), n, _ptr(n_dev), _ptr(keys), _ptr(win), _ptr(nsib),
+        self._check(n_dev, itemsize=8)
+        self._call("crdt_map_read", 0 if lww else 1, _ref(t), n, _ptr(n_dev), _ptr(keys), _ptr(win), _ptr(nsib),
                    count.data_ptr())
         return keys, win, nsib, count
 
@@ -605,14 +598,11 @@ class Engine:
         self._check(probes, win, itemsize=8)
         if win.dtype != torch.int64 or win.numel() < m:
             raise ValueError("map_lookup: win must be int64 and hold one entry per probe")
-        if nsib is not None:
-            self._check(nsib, itemsize=4)
-            if nsib.numel() < m:
-                raise ValueError("map_lookup: nsib holds fewer entries than there are probes")
-        if n_dev is not None:
-            self._check(n_dev, itemsize=8)
-        ct = t.c()
-        self._call("crdt_map_lookup", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev), _ptr(probes), m, _ptr(win),
+        self._check(nsib, itemsize=4)
+        if nsib is not None and nsib.numel() < m:
+            raise ValueError("map_lookup: nsib holds fewer entries than there are probes")
+        self._check(n_dev, itemsize=8)
+        self._call("crdt_map_lookup", 0 if lww else 1, _ref(t), len(t), _ptr(n_dev), _ptr(probes), m, _ptr(win),
                    _ptr(nsib))
         return win, nsib
 
@@ -659,33 +649,19 @@ class Engine:
         sliced results returned."""
         out, src, ctx_out = self._causal_outputs("causal_merge", a, ctx_a, b, ctx_b, out, src, ctx_out, with_src)
         count = self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out, count)
-        return self._causal_result(out, src, ctx_out, count, trim)
+        return self._result(trim, count, out, src, ctx_out)
 
     def _causal_outputs(self, who: str, a: TupleSet, ctx_a, b: TupleSet, ctx_b, out, src, ctx_out, with_src: bool):
         """The output buffers of a causal merge, allocated where not given and checked where given."""
         n = len(a) + len(b)
-        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
-        if len(out) < n:
-            raise ValueError(f"{who}: out holds fewer tuples than len(a) + len(b)")
-        if src is None and with_src:
-            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
-        if src is not None:
-            self._check(src, itemsize=8)
-            if src.dtype != torch.int64 or src.numel() < n:
-                raise ValueError(f"{who}: src must be int64 and hold len(a) + len(b) entries")
+        out = self._out_tuples(out, n, f"{who}: out holds fewer tuples than len(a) + len(b)")
+        src = self._out_src(src, with_src, n, f"{who}: src must be int64 and hold len(a) + len(b) entries")
         nc = max(0 if ctx_a is None else ctx_a.numel(), 0 if ctx_b is None else ctx_b.numel())
         ctx_out = torch.empty(nc, dtype=torch.int64, device=self.device) if ctx_out is None else ctx_out
         self._check(ctx_out, itemsize=8)
         if ctx_out.numel() < nc:
             raise ValueError(f"{who}: ctx_out holds fewer entries than the longer context")
         return out, src, ctx_out
-
-    def _causal_result(self, out: TupleSet, src, ctx_out, count, trim: bool):
-        if trim:
-            self.check_device()
-            k = int(count.item())
-            return (out.slice(k), ctx_out, count) if src is None else (out.slice(k), src[:k], ctx_out, count)
-        return (out, ctx_out, count) if src is None else (out, src, ctx_out, count)
 
     def causal_merge_count(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet, ctx_b: torch.Tensor | None,
                            n_a_dev: torch.Tensor | None = None, n_b_dev: torch.Tensor | None = None,
@@ -697,15 +673,10 @@ class Engine:
     def _causal_merge(self, a: TupleSet, ctx_a, b: TupleSet, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out, count,
                       ranges=None) -> torch.Tensor:
         """crdt_orset_merge_causal, or with ranges = (splitters, flags) crdt_orset_merge_causal_ranges."""
-        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        count = self._count(count)
         self._check(count, itemsize=8)
-        for s in (a, b) + (() if out is None else (out,)):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        for x in (ctx_a, ctx_b, n_a_dev, n_b_dev):
-            if x is not None:
-                self._check(x, itemsize=8)
+        self._check_tuples(a, b, out)
+        self._check(ctx_a, ctx_b, n_a_dev, n_b_dev, itemsize=8)
         fn, mid = "crdt_orset_merge_causal", ()
         if ranges is not None:
             splitters, flags = ranges
@@ -713,14 +684,11 @@ class Engine:
             self._check(flags, itemsize=1)
             if flags.numel() < m + 1:
                 raise ValueError("causal_merge_ranges: flags must hold len(splitters) + 1 entries")
-            if splitters is not None:
-                self._check(splitters, itemsize=8)
+            self._check(splitters, itemsize=8)
             fn, mid = "crdt_orset_merge_causal_ranges", (_ptr(splitters) if m else None, m, _ptr(flags))
-        ca, cb = a.c(), b.c()
-        co = None if out is None else out.c()
-        self._call(fn, C.byref(ca), len(a), _ptr(n_a_dev), _ptr(ctx_a), 0 if ctx_a is None else ctx_a.numel(),
-                   C.byref(cb), len(b), _ptr(n_b_dev), _ptr(ctx_b), 0 if ctx_b is None else ctx_b.numel(), *mid,
-                   None if co is None else C.byref(co), _ptr(src), _ptr(ctx_out), count.data_ptr())
+        self._call(fn, _ref(a), len(a), _ptr(n_a_dev), _ptr(ctx_a), 0 if ctx_a is None else ctx_a.numel(),
+                   _ref(b), len(b), _ptr(n_b_dev), _ptr(ctx_b), 0 if ctx_b is None else ctx_b.numel(), *mid,
+                   _ref(out), _ptr(src), _ptr(ctx_out), count.data_ptr())
         return count
 
     def causal_map_merge(self, a: TupleSet, a_val: torch.Tensor, ctx_a: torch.Tensor | None, b: TupleSet,
@@ -762,22 +730,11 @@ class Engine:
         the device status is checked and the sliced results returned; without
         it everything stays on the device, no synchronisation."""
         n = len(t) + op_keys.numel()
-        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
-        if len(out) < n:
-            raise ValueError("set_apply: out holds fewer tuples than len(t) + len(op_keys)")
-        if src is None and with_src:
-            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
-        if src is not None:
-            self._check(src, itemsize=8)
-            if src.dtype != torch.int64 or src.numel() < n:
-                raise ValueError("set_apply: src must be int64 and hold len(t) + len(op_keys) entries")
+        out = self._out_tuples(out, n, "set_apply: out holds fewer tuples than len(t) + len(op_keys)")
+        src = self._out_src(src, with_src, n, "set_apply: src must be int64 and hold len(t) + len(op_keys) entries")
         clock_out = torch.empty(clock.numel(), dtype=torch.int64, device=self.device) if clock_out is None else clock_out
         count = self._set_apply(t, clock, rep, op_keys, op_kinds, causal, n_dev, out, src, clock_out, count)
-        if trim:
-            self.check_device()
-            k = int(count.item())
-            return (out.slice(k), clock_out, count) if src is None else (out.slice(k), src[:k], clock_out, count)
-        return (out, clock_out, count) if src is None else (out, src, clock_out, count)
+        return self._result(trim, count, out, src, clock_out)
 
     def set_apply_count(self, t: TupleSet, clock: torch.Tensor, rep: int, op_keys: torch.Tensor,
                         op_kinds: torch.Tensor, causal: bool, n_dev: torch.Tensor | None = None,
@@ -789,7 +746,7 @@ class Engine:
 
     def _set_apply(self, t: TupleSet, clock, rep: int, op_keys, op_kinds, causal: bool, n_dev, out, src, clock_out,
                    count) -> torch.Tensor:
-        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        count = self._count(count)
         self._check(count, clock, op_keys, itemsize=8)
         self._check(op_kinds, itemsize=1)
         m = op_keys.numel()
@@ -797,20 +754,13 @@ class Engine:
             raise ValueError("set_apply: one kind per operation key")
         if not 0 <= rep < 2 ** 32:
             raise ValueError("set_apply: rep is a uint32")
-        for s in (t,) + (() if out is None else (out,)):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        for x in (n_dev, clock_out):
-            if x is not None:
-                self._check(x, itemsize=8)
+        self._check_tuples(t, out)
+        self._check(n_dev, clock_out, itemsize=8)
         if clock_out is not None and clock_out.numel() < clock.numel():
             raise ValueError("set_apply: clock_out holds fewer entries than clock")
-        ct = t.c()
-        co = None if out is None else out.c()
-        self._call("crdt_set_apply", 1 if causal else 0, C.byref(ct), len(t), _ptr(n_dev), _ptr(clock), clock.numel(),
-                   rep, _ptr(op_keys) if m else None, _ptr(op_kinds) if m else None, m,
-                   None if co is None else C.byref(co), _ptr(src), _ptr(clock_out), count.data_ptr())
+        self._call("crdt_set_apply", 1 if causal else 0, _ref(t), len(t), _ptr(n_dev), _ptr(clock), clock.numel(),
+                   rep, _ptr(op_keys) if m else None, _ptr(op_kinds) if m else None, m, _ref(out), _ptr(src),
+                   _ptr(clock_out), count.data_ptr())
         return count
 
     def map_apply(self, t: TupleSet, val: torch.Tensor, clock: torch.Tensor, rep: int, op_keys: torch.Tensor,
@@ -853,7 +803,7 @@ class Engine:
         out, src, ctx_out = self._causal_outputs("causal_merge_ranges", a, ctx_a, b, ctx_b, out, src, ctx_out, with_src)
         count = self._causal_merge(a, ctx_a, b, ctx_b, n_a_dev, n_b_dev, out, src, ctx_out, count,
                                    ranges=(splitters, flags))
-        return self._causal_result(out, src, ctx_out, count, trim)
+        return self._result(trim, count, out, src, ctx_out)
 
     def causal_merge_ranges_count(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet,
                                   ctx_b: torch.Tensor | None, splitters: torch.Tensor | None, flags: torch.Tensor,
@@ -881,12 +831,6 @@ class Engine:
 
     # -- range digests: where two states differ, without shipping either
     #    (crdt_set_digest / crdt_set_digest_diff / crdt_set_select)
-    def _check_tuples(self, *sets: TupleSet) -> None:
-        for s in sets:
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-
     def set_digest(self, t: TupleSet, lww: bool, splitters: torch.Tensor | None, n_dev: torch.Tensor | None = None,
                    hash_out: torch.Tensor | None = None, count_out: torch.Tensor | None = None):
         """One order-independent fingerprint per key range of the sorted set
@@ -907,11 +851,8 @@ class Engine:
         self._check(hash_out, count_out, itemsize=8)
         if hash_out.numel() < m + 1 or count_out.numel() < m + 1:
             raise ValueError("set_digest: the outputs must hold len(splitters) + 1 entries")
-        for x in (splitters, n_dev):
-            if x is not None:
-                self._check(x, itemsize=8)
-        ct = t.c()
-        self._call("crdt_set_digest", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev),
+        self._check(splitters, n_dev, itemsize=8)
+        self._call("crdt_set_digest", 0 if lww else 1, _ref(t), len(t), _ptr(n_dev),
                    _ptr(splitters) if m else None, m, hash_out.data_ptr(), count_out.data_ptr())
         return hash_out, count_out
 
@@ -926,7 +867,7 @@ class Engine:
         if not (ca.numel() == hb.numel() == cb.numel() == nb):
             raise ValueError("digest_diff: the four arrays differ in length")
         flags = torch.empty(max(nb, 1), dtype=torch.uint8, device=self.device) if flags is None else flags
-        n_diff = torch.empty(1, dtype=torch.int64, device=self.device) if n_diff is None else n_diff
+        n_diff = self._count(n_diff)
         self._check(ha, ca, hb, cb, n_diff, itemsize=8)
         self._check(flags, itemsize=1)
         if flags.numel() < nb:
@@ -943,21 +884,10 @@ class Engine:
         differing ranges.  Returns (out, count), or (out, src, count) with
         ``with_src`` (or a ``src`` tensor), as :meth:`set_compact` does."""
         n = len(t)
-        out = TupleSet.empty(max(n, 1), self.device) if out is None else out
-        if len(out) < n:
-            raise ValueError("set_select: out holds fewer tuples than t")
-        if src is None and with_src:
-            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
-        if src is not None:
-            self._check(src, itemsize=8)
-            if src.dtype != torch.int64 or src.numel() < n:
-                raise ValueError("set_select: src must be int64 and hold len(t) entries")
+        out = self._out_tuples(out, n, "set_select: out holds fewer tuples than t")
+        src = self._out_src(src, with_src, n, "set_select: src must be int64 and hold len(t) entries")
         count = self._set_select(t, lww, splitters, flags, n_dev, out, src, count)
-        if trim:
-            self.check_device()
-            k = int(count.item())
-            return (out.slice(k), count) if src is None else (out.slice(k), src[:k], count)
-        return (out, count) if src is None else (out, src, count)
+        return self._result(trim, count, out, src)
 
     def set_select_count(self, t: TupleSet, lww: bool, splitters: torch.Tensor | None, flags: torch.Tensor,
                          n_dev: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
@@ -966,21 +896,16 @@ class Engine:
         return self._set_select(t, lww, splitters, flags, n_dev, None, None, count)
 
     def _set_select(self, t: TupleSet, lww: bool, splitters, flags, n_dev, out, src, count) -> torch.Tensor:
-        count = torch.empty(1, dtype=torch.int64, device=self.device) if count is None else count
+        count = self._count(count)
         m = 0 if splitters is None else splitters.numel()
         self._check(count, itemsize=8)
         self._check(flags, itemsize=1)
         if flags.numel() < m + 1:
             raise ValueError("set_select: flags must hold len(splitters) + 1 entries")
-        self._check_tuples(*((t,) + (() if out is None else (out,))))
-        for x in (splitters, n_dev):
-            if x is not None:
-                self._check(x, itemsize=8)
-        ct = t.c()
-        co = None if out is None else out.c()
-        self._call("crdt_set_select", 0 if lww else 1, C.byref(ct), len(t), _ptr(n_dev),
-                   _ptr(splitters) if m else None, m, _ptr(flags), None if co is None else C.byref(co), _ptr(src),
-                   count.data_ptr())
+        self._check_tuples(t, out)
+        self._check(splitters, n_dev, itemsize=8)
+        self._call("crdt_set_select", 0 if lww else 1, _ref(t), len(t), _ptr(n_dev), _ptr(splitters) if m else None,
+                   m, _ptr(flags), _ref(out), _ptr(src), count.data_ptr())
         return count
 
     def map_select(self, t: TupleSet, val: torch.Tensor, lww: bool, splitters: torch.Tensor | None,
@@ -1011,18 +936,13 @@ class Engine:
         """Stable merge of two sorted tuple arrays, every tuple kept (a's
         copies first on an equal tag): crdt_tuples_merge."""
         out = TupleSet.empty(max(len(a) + len(b), 1), self.device) if out is None else out
-        for s in (a, b, out):
-            self._check(s.key, s.ts, itemsize=8)
-            self._check(s.rep, itemsize=4)
-            self._check(s.tomb, itemsize=1)
-        ca, cb, co = a.c(), b.c(), out.c()
-        self._call("crdt_tuples_merge", C.byref(ca), len(a), C.byref(cb), len(b), C.byref(co))
+        self._check_tuples(a, b, out)
+        self._call("crdt_tuples_merge", _ref(a), len(a), _ref(b), len(b), _ref(out))
         return out.slice(len(a) + len(b))
 
     def count_unsorted(self, t: TupleSet) -> int:
-        bad = torch.empty(1, dtype=torch.int64, device=self.device)
-        ct = t.c()
-        self._call("crdt_tuples_count_unsorted", C.byref(ct), len(t), bad.data_ptr())
+        bad = self._count(None)
+        self._call("crdt_tuples_count_unsorted", _ref(t), len(t), bad.data_ptr())
         return int(bad.item())
 
     # ------------------------------------------------------------ RefMerge (a1-a3)
