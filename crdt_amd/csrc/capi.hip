@@ -46,6 +46,24 @@ int ws_reserve(crdt_ctx *ctx, size_t bytes) {
         return hip_fail(ctx, e);
     }
     ctx->ws_bytes = want;
+    return scratch_fill(ctx, ctx->ws, want);        // (diagnostic build: a grown workspace starts from the fill byte)
+}
+
+// "ctx.ws_fill" >= 0 (diagnostic build): the byte over [p, p + bytes) on the
+// context's stream, counted in "ctx.ws_filled_mb".  The product build folds
+// it away.
+int scratch_fill(crdt_ctx *ctx, void *p, size_t bytes) {
+#ifdef CRDT_DIAG
+    if (g_ws_fill < 0 || !p || bytes == 0) return CRDT_OK;
+    hipError_t e = hipMemsetAsync(p, g_ws_fill, bytes, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e);
+    static size_t part = 0;                          // the bytes below a whole MiB, carried to the next fill
+    part += bytes;
+    g_ws_filled_mb += (int)(part >> 20);
+    part &= (1u << 20) - 1;
+#else
+    (void)ctx, (void)p, (void)bytes;
+#endif
     return CRDT_OK;
 }
 
@@ -310,7 +328,13 @@ extern "C" int crdt_ctx_last_hip_error(const crdt_ctx *ctx) { return ctx ? ctx->
 extern "C" int crdt_ctx_reserve(crdt_ctx *ctx, size_t bytes) {
     int rc = bind(ctx);
     if (rc) return rc;
-    return ws_reserve(ctx, bytes);
+    const size_t had = ctx->ws_bytes;
+    rc = ws_reserve(ctx, bytes);
+    // (diagnostic build, "ctx.ws_fill": the whole workspace starts every later
+    // call from the fill byte -- nothing in it outlives a call; a workspace
+    // that grew just now is filled already)
+    if (!rc && ctx->ws_bytes == had) rc = scratch_fill(ctx, ctx->ws, ctx->ws_bytes);
+    return rc;
 }
 
 // The knob table (knobs.inc): name, current value, validity of a new value.

@@ -53,3 +53,9 @@ KNOB(g_pop_wire_early, 1, "pop.wire_early", v == 0 || v == 1)
 KNOB(g_read_poll, 1, "ctx.read_poll", v == 0 || v == 1)
 KNOB(g_scan_items, 8, "scan.items", v == 4 || v == 8 || v == 16)
 KNOB(g_tile_scan_round, 16384, "settile.scan_round", v == 1024 || v == 16384)
+// Scratch fill (tests/test_gpu_ws_fill.py; DESIGN.md §5.22): a value >= 0 is the
+// byte crdt_ctx_reserve writes over the whole workspace, and that a grown
+// workspace or shard scratch starts from.  ctx.ws_filled_mb counts the MiB
+// filled so far in the process (read it; setting it to 0 resets it).
+KNOB(g_ws_fill, -1, "ctx.ws_fill", v >= -1 && v <= 255)
+KNOB(g_ws_filled_mb, 0, "ctx.ws_filled_mb", v == 0)

@@ -407,7 +407,7 @@ int scratch_reserve(crdt_comm::Member &mb, size_t bytes) {
         return hip_fail(mb.ctx, e);
     }
     mb.scratch_bytes = want;
-    return CRDT_OK;
+    return scratch_fill(mb.ctx, mb.scratch, want);
 }
 
 int sync_all(crdt_comm *c) {
@@ -656,7 +656,14 @@ extern "C" int crdt_shard_comm_last_error(const crdt_comm *c) { return c ? c->la
 
 extern "C" int crdt_shard_sync(crdt_comm *c) {
     if (!valid(c)) return CRDT_E_INVAL;
-    return sync_all(c);
+    int rc = sync_all(c);
+    // (diagnostic build, "ctx.ws_fill": no member's scratch carries anything
+    // from one call to the next, so each starts the next call from the fill byte)
+    for (size_t i = 0; i < c->m.size() && !rc; ++i) {
+        rc = bind(c->m[i].ctx);
+        if (!rc) rc = scratch_fill(c->m[i].ctx, c->m[i].scratch, c->m[i].scratch_bytes);
+    }
+    return rc;
 }
 
 // buf[i] (member i, n uint64 on its device) := elementwise unsigned max over
