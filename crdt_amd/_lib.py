@@ -68,6 +68,11 @@ class crdt_tuples(C.Structure):
     _fields_ = [("key", C.c_void_p), ("ts", C.c_void_p), ("rep", C.c_void_p), ("tomb", C.c_void_p)]
 
 
+class crdt_cmap(C.Structure):
+    """Cells of a keyed PN-Counter map: (key u64, rep u32, p u64, n u64) columns."""
+    _fields_ = [("key", C.c_void_p), ("rep", C.c_void_p), ("p", C.c_void_p), ("n", C.c_void_p)]
+
+
 class crdt_refmerge_in(C.Structure):
     _fields_ = [
         ("replicas", C.c_uint32), ("n_slots", C.c_uint32),
@@ -175,6 +180,14 @@ SIGNATURES = {
     "crdt_stream_read": (_I, [_CTX, _P, _SZ, _P, _SZ, _I, _I]),
     "crdt_pncounter_join": (_I, [_CTX, _P, _P, _P, _P, _P, _P, _SZ, _SZ]),
     "crdt_pncounter_value": (_I, [_CTX, _P, _P, _P, _SZ, _SZ]),
+    "crdt_cmap_merge": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, C.POINTER(crdt_cmap), _SZ, _P, C.POINTER(crdt_cmap),
+                             _P]),
+    "crdt_cmap_apply": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, C.c_uint32, _P, _P, _P, _SZ, C.POINTER(crdt_cmap),
+                             _P]),
+    "crdt_cmap_values": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, _P, _P, _P, _P, _P]),
+    "crdt_cmap_lookup": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, _P, _SZ, _P, _P]),
+    "crdt_cmap_delta": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, C.POINTER(crdt_cmap), _SZ, _P, C.POINTER(crdt_cmap),
+                             _P]),
     "crdt_vclock_classify": (_I, [_CTX, _P, _P, _P, _SZ, _SZ]),
     "crdt_lww_merge": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, C.POINTER(crdt_tuples), _SZ,
                             C.POINTER(crdt_tuples), _P]),

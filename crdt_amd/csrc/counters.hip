@@ -1,11 +1,13 @@
-// counters.hip -- G-Counter / PN-Counter / vector-clock join kernels.
+// counters.hip -- dense and keyed counters: the G-Counter / PN-Counter /
+// vector-clock join kernels and the entry points of the keyed
+// PN-Counter map (crdt_cmap_*; kernels in countermap.hpp).
 //
 // No reference code exists for these types: they are the
 // standard state-based CRDT joins (elementwise unsigned max) over a replica
-// population stored row-major [rows x nodes] uint64 in HBM.  Everything here
-// is HBM-bound integer streaming: 16-byte (dwordx4) loads per lane, several
-// independent loads in flight per lane, no LDS, no MFMA.
-#include "common.hpp"
+// population stored row-major [rows x nodes] uint64 in HBM.  Everything dense
+// here is HBM-bound integer streaming: 16-byte (dwordx4) loads per lane,
+// several independent loads in flight per lane, no LDS, no MFMA.
+#include "countermap.hpp"
 
 namespace crdt {
 
@@ -404,5 +406,251 @@ extern "C" int crdt_ordered_i64_to_u64(crdt_ctx *ctx, const int64_t *in, uint64_
     if (n == 0) return CRDT_OK;
     if (!in || !out) return CRDT_E_INVAL;
     k_i64_to_u64<<<grid_for(n, 256, 4096), 256, 0, ctx->stream>>>(in, out, n);
+    return check_launch(ctx);
+}
+
+// ---------------------------------------------------------------- keyed PN-Counter map
+// Entry points of crdt_cmap_* (include/crdt_amd.h; kernels and pass structure:
+// countermap.hpp).  Every length may stay on the device; every call is
+// stream-ordered with no host synchronisation.
+static bool cmap_null(const crdt_cmap *t) { return !t->key || !t->rep || !t->p || !t->n; }
+static bool cmap_misaligned(const crdt_cmap *t) {
+    return ((((uintptr_t)t->key | (uintptr_t)t->p | (uintptr_t)t->n) & 7) | ((uintptr_t)t->rep & 3)) != 0;
+}
+struct CmSpan {
+    const void *p;
+    size_t bytes;
+};
+static int cmap_fields(const crdt_cmap *t, size_t n, CmSpan *s) {
+    s[0] = {t->key, n * 8};
+    s[1] = {t->rep, n * 4};
+    s[2] = {t->p, n * 8};
+    s[3] = {t->n, n * 8};
+    return 4;
+}
+// an output meets an input or another output
+static bool cmap_clash(const CmSpan *o, int no, const CmSpan *in, int ni) {
+    for (int x = 0; x < no; ++x) {
+        for (int y = 0; y < ni; ++y)
+            if (spans_overlap(o[x].p, o[x].bytes, in[y].p, in[y].bytes)) return true;
+        for (int y = x + 1; y < no; ++y)
+            if (spans_overlap(o[x].p, o[x].bytes, o[y].p, o[y].bytes)) return true;
+    }
+    return false;
+}
+// the split's view of a side: key and rep (the other two fields are never dereferenced)
+static crdt_tuples cmap_view(const crdt_cmap &c) {
+    crdt_tuples v;
+    v.key = c.key;
+    v.ts = nullptr;
+    v.rep = c.rep;
+    v.tomb = nullptr;
+    return v;
+}
+
+// split -> count -> scan -> write of one two-sided call over the carved tiles.
+// DELTA: side a = dst, b = src, out holds src cells; else out = the union, a
+// cell of both sides combined by Comb.
+template <bool DELTA, class Comb>
+static int cmap_two_sided(crdt_ctx *ctx, const TileWs &w, size_t ntiles, const crdt_cmap &A, size_t na_max,
+                          const uint64_t *na_dev, const crdt_cmap &B, size_t nb_max, const uint64_t *nb_dev,
+                          const crdt_cmap *out, uint64_t *count) {
+    using Tiles = typename std::conditional<DELTA, CmDeltaTiles, PlainTiles>::type;
+    const bool wr = out != nullptr;
+    const hipStream_t s = ctx->stream;
+    if (ntiles) {
+        const unsigned g = (unsigned)ntiles;
+        k_mp_split<CT, CellLe, Tiles><<<mp_split_grid(ntiles), 256, 0, s>>>(cmap_view(A), na_max, na_dev, cmap_view(B),
+                                                                           nb_max, nb_dev, w.split);
+        if (wr)
+            k_cmap_count<DELTA, true, Tiles><<<g, CCB, 0, s>>>(A, na_max, na_dev, B, nb_max, nb_dev, w.split, w.tcnt, w.bits);
+        else
+            k_cmap_count<DELTA, false, Tiles><<<g, CCB, 0, s>>>(A, na_max, na_dev, B, nb_max, nb_dev, w.split, w.tcnt, w.bits);
+    }
+    w.scan<NoCarry<Tiles>>(ctx, na_max, na_dev, nb_max, nb_dev, wr, count);
+    if (ntiles && wr) {
+        const unsigned g = (unsigned)ntiles;
+        if (DELTA)
+            k_cmap_delta_write<<<g, CWB, 0, s>>>(B, nb_max, nb_dev, na_max, na_dev, w.split, w.bits, w.ic, *out,
+                                                 ctx->dev_status);
+        else
+            k_cmap_write<Comb><<<g, CWB, 0, s>>>(A, na_max, na_dev, B, nb_max, nb_dev, w.split, w.bits, w.ic, *out,
+                                                 ctx->dev_status);
+    }
+    return check_launch(ctx);
+}
+
+extern "C" int crdt_cmap_merge(crdt_ctx *ctx, const crdt_cmap *a, size_t na_max, const uint64_t *na_dev,
+                               const crdt_cmap *b, size_t nb_max, const uint64_t *nb_dev, const crdt_cmap *out,
+                               uint64_t *count_dev) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!a || !b || !count_dev) return CRDT_E_INVAL;
+    if (na_max >= (1ULL << 62) || nb_max >= (1ULL << 62)) return CRDT_E_RANGE;
+    if ((na_max && cmap_null(a)) || (nb_max && cmap_null(b))) return CRDT_E_INVAL;
+    if (cmap_misaligned(a) || cmap_misaligned(b) || (out && cmap_misaligned(out))) return CRDT_E_INVAL;
+    if ((((uintptr_t)na_dev | (uintptr_t)nb_dev | (uintptr_t)count_dev) & 7) != 0) return CRDT_E_INVAL;
+    const size_t cap = na_max + nb_max;
+    const size_t ntiles = (cap + CT - 1) / CT;
+    if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;   // (so no byte count below wraps)
+    if (out && cap && cmap_null(out)) return CRDT_E_INVAL;
+    {
+        CmSpan in[10], o[5];
+        int ni = cmap_fields(a, na_max, in), no = 0;
+        ni += cmap_fields(b, nb_max, in + ni);
+        in[ni++] = {na_dev, 8};
+        in[ni++] = {nb_dev, 8};
+        if (out) no = cmap_fields(out, cap, o);
+        o[no++] = {count_dev, 8};
+        if (cmap_clash(o, no, in, ni)) return CRDT_E_INVAL;
+    }
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, true, false, CBS);
+    if (rc) return rc;
+    return cmap_two_sided<false, CmMax>(ctx, w, ntiles, *a, na_max, na_dev, *b, nb_max, nb_dev, out, count_dev);
+}
+
+extern "C" int crdt_cmap_apply(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev, uint32_t rep,
+                               const uint64_t *op_key_dev, const uint64_t *op_dp_dev, const uint64_t *op_dn_dev,
+                               size_t m, const crdt_cmap *out, uint64_t *count_dev) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!t || !count_dev) return CRDT_E_INVAL;
+    if (n_max >= (1ULL << 62) || m >= (1ULL << 62)) return CRDT_E_RANGE;
+    if (n_max && cmap_null(t)) return CRDT_E_INVAL;
+    if (m && (!op_key_dev || !op_dp_dev || !op_dn_dev)) return CRDT_E_INVAL;
+    if (cmap_misaligned(t) || (out && cmap_misaligned(out))) return CRDT_E_INVAL;
+    if ((((uintptr_t)op_key_dev | (uintptr_t)op_dp_dev | (uintptr_t)op_dn_dev | (uintptr_t)n_dev |
+          (uintptr_t)count_dev) & 7) != 0)
+        return CRDT_E_INVAL;
+    const size_t cap = n_max + m;
+    const size_t ntiles = (cap + CT - 1) / CT;
+    if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;   // (so no byte count below wraps)
+    if (out && cap && cmap_null(out)) return CRDT_E_INVAL;
+    {
+        CmSpan in[8], o[5];
+        int ni = cmap_fields(t, n_max, in), no = 0;
+        in[ni++] = {n_dev, 8};
+        in[ni++] = {op_key_dev, m * 8};
+        in[ni++] = {op_dp_dev, m * 8};
+        in[ni++] = {op_dn_dev, m * 8};
+        if (out) no = cmap_fields(out, cap, o);
+        o[no++] = {count_dev, 8};
+        if (cmap_clash(o, no, in, ni)) return CRDT_E_INVAL;
+    }
+    // behind the tiles: the batch's rep column, so that the batch is an ordinary side
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, true, false, CBS, Carve::round(m * 4) + 256);
+    if (rc) return rc;
+    Carve x((char *)ctx->ws + TileWs::bytes(ntiles, true, false, CBS));
+    crdt_cmap B;
+    B.key = const_cast<uint64_t *>(op_key_dev);
+    B.rep = x.take<uint32_t>(m);
+    B.p = const_cast<uint64_t *>(op_dp_dev);
+    B.n = const_cast<uint64_t *>(op_dn_dev);
+    if (m) {
+        const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)B.rep, (int)rep, m, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e);
+    }
+    return cmap_two_sided<false, CmAdd>(ctx, w, ntiles, *t, n_max, n_dev, B, m, nullptr, out, count_dev);
+}
+
+extern "C" int crdt_cmap_delta(crdt_ctx *ctx, const crdt_cmap *src, size_t ns_max, const uint64_t *ns_dev,
+                               const crdt_cmap *dst, size_t nd_max, const uint64_t *nd_dev, const crdt_cmap *out,
+                               uint64_t *count_dev) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!src || !dst || !count_dev) return CRDT_E_INVAL;
+    if (ns_max >= (1ULL << 62) || nd_max >= (1ULL << 62)) return CRDT_E_RANGE;
+    if ((ns_max && cmap_null(src)) || (nd_max && cmap_null(dst))) return CRDT_E_INVAL;
+    if (cmap_misaligned(src) || cmap_misaligned(dst) || (out && cmap_misaligned(out))) return CRDT_E_INVAL;
+    if ((((uintptr_t)ns_dev | (uintptr_t)nd_dev | (uintptr_t)count_dev) & 7) != 0) return CRDT_E_INVAL;
+    const size_t ntiles = ns_max ? (ns_max + nd_max + CT - 1) / CT : 0;
+    if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;   // (so no byte count below wraps)
+    if (out && ns_max && cmap_null(out)) return CRDT_E_INVAL;
+    {
+        CmSpan in[10], o[5];
+        int ni = cmap_fields(src, ns_max, in), no = 0;
+        ni += cmap_fields(dst, nd_max, in + ni);
+        in[ni++] = {ns_dev, 8};
+        in[ni++] = {nd_dev, 8};
+        if (out) no = cmap_fields(out, ns_max, o);
+        o[no++] = {count_dev, 8};
+        if (cmap_clash(o, no, in, ni)) return CRDT_E_INVAL;
+    }
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, true, false, CBS);
+    if (rc) return rc;
+    // side a = dst: its copy of a shared cell is merged first
+    return cmap_two_sided<true, CmMax>(ctx, w, ntiles, *dst, nd_max, nd_dev, *src, ns_max, ns_dev, out, count_dev);
+}
+
+extern "C" int crdt_cmap_values(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev,
+                                uint64_t *keys_out, uint64_t *p_out, uint64_t *n_out, int64_t *value_out,
+                                uint64_t *count_dev) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!t || !count_dev) return CRDT_E_INVAL;
+    if (n_max >= (1ULL << 62)) return CRDT_E_RANGE;
+    if (n_max && cmap_null(t)) return CRDT_E_INVAL;
+    if (cmap_misaligned(t)) return CRDT_E_INVAL;
+    if ((((uintptr_t)keys_out | (uintptr_t)p_out | (uintptr_t)n_out | (uintptr_t)value_out | (uintptr_t)n_dev |
+          (uintptr_t)count_dev) & 7) != 0)
+        return CRDT_E_INVAL;
+    const size_t ntiles = (n_max + RT - 1) / RT;
+    if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;   // (so no byte count below wraps)
+    {
+        CmSpan in[5], o[5];
+        int ni = cmap_fields(t, n_max, in);
+        in[ni++] = {n_dev, 8};
+        o[0] = {keys_out, n_max * 8};
+        o[1] = {p_out, n_max * 8};
+        o[2] = {n_out, n_max * 8};
+        o[3] = {value_out, n_max * 8};
+        o[4] = {count_dev, 8};
+        if (cmap_clash(o, 5, in, ni)) return CRDT_E_INVAL;
+    }
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, false, false, RNW);
+    if (rc) return rc;
+    const bool sums = p_out || n_out || value_out, wr = sums || keys_out;
+    const hipStream_t s = ctx->stream;
+    const unsigned g = (unsigned)ntiles;
+    if (ntiles) {
+        if (wr) k_cmap_heads<true><<<g, RB, 0, s>>>(t->key, n_max, n_dev, w.tcnt, w.bits);
+        else k_cmap_heads<false><<<g, RB, 0, s>>>(t->key, n_max, n_dev, w.tcnt, w.bits);
+    }
+    w.scan<NoCarry<>>(ctx, n_max, n_dev, 0, nullptr, wr, count_dev);
+    if (ntiles && keys_out)
+        k_tile_write_field<uint64_t><<<g, kTileB, 0, s>>>(t->key, n_max, n_dev, w.bits, w.ic, keys_out, ctx->dev_status);
+    if (ntiles && sums) {
+        if (ntiles > 1)
+            k_cmap_zero<<<(unsigned)((ntiles + 255) / 256), 256, 0, s>>>(n_max, n_dev, w.bits, w.ic, p_out, n_out, value_out);
+        k_cmap_sums<<<g, RB, 0, s>>>(t->p, t->n, n_max, n_dev, w.bits, w.ic, p_out, n_out, value_out, ctx->dev_status);
+    }
+    return check_launch(ctx);
+}
+
+extern "C" int crdt_cmap_lookup(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev,
+                                const uint64_t *probes_dev, size_t m, int64_t *value_out, uint8_t *found_out) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!t) return CRDT_E_INVAL;
+    if (n_max >= (1ULL << 62) || m >= (1ULL << 60)) return CRDT_E_RANGE;
+    if (m == 0) return CRDT_OK;
+    if (!probes_dev || !value_out || (n_max && cmap_null(t)) || cmap_misaligned(t)) return CRDT_E_INVAL;
+    if ((((uintptr_t)probes_dev | (uintptr_t)value_out | (uintptr_t)n_dev) & 7) != 0) return CRDT_E_INVAL;
+    {
+        CmSpan in[6], o[2];
+        int ni = cmap_fields(t, n_max, in);
+        in[ni++] = {n_dev, 8};
+        in[ni++] = {probes_dev, m * 8};
+        o[0] = {value_out, m * 8};
+        o[1] = {found_out, m};
+        if (cmap_clash(o, 2, in, ni)) return CRDT_E_INVAL;
+    }
+    k_cmap_lookup<<<grid_for(m, 256, (unsigned)ctx->num_cus * 8), 256, 0, ctx->stream>>>(*t, n_max, n_dev, probes_dev, m,
+                                                                                       value_out, found_out,
+                                                                                       ctx->dev_status);
     return check_launch(ctx);
 }

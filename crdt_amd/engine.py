@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (call, crdt_local_in, crdt_local_out, crdt_refmerge_acc, crdt_refmerge_in, crdt_refmerge_kv_out,
-                   crdt_refmerge_out, crdt_refmerge_pull, crdt_replay_state, crdt_tuples)
+from ._lib import (call, crdt_cmap, crdt_local_in, crdt_local_out, crdt_refmerge_acc, crdt_refmerge_in,
+                   crdt_refmerge_kv_out, crdt_refmerge_out, crdt_refmerge_pull, crdt_replay_state, crdt_tuples)
 
 VC_EQUAL, VC_BEFORE, VC_AFTER, VC_CONCURRENT = 0, 1, 2, 3
 
@@ -76,6 +76,42 @@ class TupleSet:
         return TupleSet(u64_tensor(key, device), u64_tensor(ts, device),
                         torch.from_numpy(np.ascontiguousarray(rep).view(np.int32).copy()).to(device),
                         torch.from_numpy(np.ascontiguousarray(tomb).astype(np.uint8)).to(device))
+
+
+@dataclass
+class CounterMap:
+    """SoA (key u64, rep u32, p u64, n u64) cells of a keyed PN-Counter map,
+    strictly ascending by (key, rep): replica rep's increments / decrements of key."""
+
+    key: torch.Tensor   # int64 storage of uint64 keys
+    rep: torch.Tensor   # int32 storage of uint32 replica ids
+    p: torch.Tensor     # int64 storage of uint64 increments
+    n: torch.Tensor     # int64 storage of uint64 decrements
+
+    def __len__(self) -> int:
+        return int(self.key.numel())
+
+    @staticmethod
+    def empty(n: int, device) -> "CounterMap":
+        return CounterMap(torch.empty(n, dtype=torch.int64, device=device),
+                          torch.empty(n, dtype=torch.int32, device=device),
+                          torch.empty(n, dtype=torch.int64, device=device),
+                          torch.empty(n, dtype=torch.int64, device=device))
+
+    def c(self) -> crdt_cmap:
+        return crdt_cmap(self.key.data_ptr(), self.rep.data_ptr(), self.p.data_ptr(), self.n.data_ptr())
+
+    def slice(self, n: int) -> "CounterMap":
+        return CounterMap(self.key[:n], self.rep[:n], self.p[:n], self.n[:n])
+
+    def to_numpy(self):
+        return (as_u64(self.key), self.rep.cpu().numpy().view(np.uint32), as_u64(self.p), as_u64(self.n))
+
+    @staticmethod
+    def from_numpy(key, rep, p, n, device) -> "CounterMap":
+        return CounterMap(u64_tensor(key, device),
+                          torch.from_numpy(np.ascontiguousarray(rep).view(np.int32).copy()).to(device),
+                          u64_tensor(p, device), u64_tensor(n, device))
 
 
 class Engine:
@@ -774,6 +810,151 @@ class Engine:
             raise ValueError("map_apply: one value per tuple and per operation")
         out, src, clock_out, count = self.set_apply(t, clock, rep, op_keys, op_kinds, causal, with_src=True, trim=False)
         return out, self.gather_src(src, val, op_vals, n_dev=count), clock_out, count
+
+    # -- the keyed PN-Counter map: merge, increments, reads and deltas (crdt_cmap_*)
+    def _check_cmap(self, *maps: CounterMap | None) -> None:
+        for s in maps:
+            if s is not None:
+                self._check(s.key, s.p, s.n, itemsize=8)
+                self._check(s.rep, itemsize=4)
+
+    def _out_cmap(self, out: CounterMap | None, n: int, short: str) -> CounterMap:
+        out = CounterMap.empty(max(n, 1), self.device) if out is None else out
+        if len(out) < n:
+            raise ValueError(short)
+        return out
+
+    def cmap_merge(self, a: CounterMap, b: CounterMap, n_a_dev: torch.Tensor | None = None,
+                   n_b_dev: torch.Tensor | None = None, out: CounterMap | None = None,
+                   count: torch.Tensor | None = None, trim: bool = False):
+        """The join of two counter maps: the union of their cells, a cell held
+        by both with p = max(p_a, p_b), n = max(n_a, n_b), unsigned.  Returns
+        (out, count), device-resident, no synchronisation -- out of capacity
+        len(a) + len(b), its first ``count`` cells valid.  ``n_a_dev`` /
+        ``n_b_dev`` (int64[1] on the device, e.g. another call's count): only
+        so many leading cells of that side are read; a value over the side's
+        length leaves count = 2^64 - 1 and raises CRDT_DEV_RANGE in
+        :meth:`device_status`.  With ``trim`` the device status is checked and
+        out is cut to the count."""
+        out = self._out_cmap(out, len(a) + len(b), "cmap_merge: out holds fewer cells than len(a) + len(b)")
+        count = self._cmap_merge(a, b, n_a_dev, n_b_dev, out, count)
+        return self._result(trim, count, out, None)
+
+    def cmap_merge_count(self, a: CounterMap, b: CounterMap, n_a_dev: torch.Tensor | None = None,
+                         n_b_dev: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(cmap_merge(a, b)) alone (int64[1] on the device, no
+        synchronisation): nothing is written but the count."""
+        return self._cmap_merge(a, b, n_a_dev, n_b_dev, None, count)
+
+    def _cmap_merge(self, a: CounterMap, b: CounterMap, n_a_dev, n_b_dev, out, count) -> torch.Tensor:
+        count = self._count(count)
+        self._check(count, n_a_dev, n_b_dev, itemsize=8)
+        self._check_cmap(a, b, out)
+        self._call("crdt_cmap_merge", _ref(a), len(a), _ptr(n_a_dev), _ref(b), len(b), _ptr(n_b_dev), _ref(out),
+                   count.data_ptr())
+        return count
+
+    def cmap_apply(self, t: CounterMap, rep: int, op_keys: torch.Tensor, op_dp: torch.Tensor, op_dn: torch.Tensor,
+                   n_dev: torch.Tensor | None = None, out: CounterMap | None = None,
+                   count: torch.Tensor | None = None, trim: bool = False):
+        """Replica ``rep``'s batch of increments applied to the counter map
+        ``t``: ``op_keys`` (int64 storage of uint64, strictly ascending),
+        ``op_dp`` / ``op_dn`` (int64 storage of uint64) on the device.  Cell
+        (op_keys[i], rep) becomes (p + op_dp[i], n + op_dn[i]) mod 2^64; an
+        absent cell is created from (0, 0).  Returns (out, count) as
+        :meth:`cmap_merge` does, out of capacity len(t) + len(op_keys)."""
+        m = op_keys.numel()
+        out = self._out_cmap(out, len(t) + m, "cmap_apply: out holds fewer cells than len(t) + len(op_keys)")
+        count = self._count(count)
+        self._check(count, op_keys, op_dp, op_dn, n_dev, itemsize=8)
+        if op_dp.numel() != m or op_dn.numel() != m:
+            raise ValueError("cmap_apply: one dp and one dn per operation key")
+        if not 0 <= rep < 2 ** 32:
+            raise ValueError("cmap_apply: rep is a uint32")
+        self._check_cmap(t, out)
+        self._call("crdt_cmap_apply", _ref(t), len(t), _ptr(n_dev), rep, _ptr(op_keys) if m else None,
+                   _ptr(op_dp) if m else None, _ptr(op_dn) if m else None, m, _ref(out), count.data_ptr())
+        return self._result(trim, count, out, None)
+
+    def cmap_values(self, t: CounterMap, n_dev: torch.Tensor | None = None, keys: torch.Tensor | None = None,
+                    p: torch.Tensor | None = None, n: torch.Tensor | None = None, value: torch.Tensor | None = None,
+                    count: torch.Tensor | None = None, trim: bool = False):
+        """One row per distinct key of ``t``, in key order: returns (keys, P,
+        N, value, count), device tensors (int64 storage) of capacity len(t)
+        whose first ``count`` rows are valid, no synchronisation -- P / N the
+        sums of the key's p / n cells mod 2^64, value = (int64)(P - N).
+        ``n_dev`` as in :meth:`cmap_merge`; with ``trim`` the device status is
+        checked and the rows are cut to the count."""
+        rows = len(t)
+        cols = []
+        for c in (keys, p, n, value):
+            c = torch.empty(max(rows, 1), dtype=torch.int64, device=self.device) if c is None else c
+            self._check(c, itemsize=8)
+            if c.numel() < rows:
+                raise ValueError("cmap_values: an output holds fewer rows than t has cells")
+            cols.append(c)
+        count = self._count(count)
+        self._check(count, n_dev, itemsize=8)
+        self._check_cmap(t)
+        self._call("crdt_cmap_values", _ref(t), rows, _ptr(n_dev), *(c.data_ptr() for c in cols), count.data_ptr())
+        if trim:
+            k = self._trimmed(count)
+            cols = [c[:k] for c in cols]
+        return (*cols, count)
+
+    def cmap_count_keys(self, t: CounterMap, n_dev: torch.Tensor | None = None,
+                        count: torch.Tensor | None = None) -> torch.Tensor:
+        """The number of distinct keys of ``t`` alone (int64[1] on the device,
+        no synchronisation): :meth:`cmap_values` with no output."""
+        count = self._count(count)
+        self._check(count, n_dev, itemsize=8)
+        self._check_cmap(t)
+        self._call("crdt_cmap_values", _ref(t), len(t), _ptr(n_dev), None, None, None, None, count.data_ptr())
+        return count
+
+    def cmap_get(self, t: CounterMap, probes: torch.Tensor, n_dev: torch.Tensor | None = None,
+                 value: torch.Tensor | None = None, found: torch.Tensor | None = None, with_found: bool = True):
+        """The counter of each probe key (uint64 in int64 storage, any order,
+        repeats allowed): returns (value, found), device tensors of
+        len(probes), no synchronisation -- value[i] (int64) is 0 and found[i]
+        (uint8) is 0 where the key is absent; found is None unless asked for.
+        A device length over len(t) gives zeros and raises CRDT_DEV_RANGE."""
+        m = probes.numel()
+        value = torch.empty(max(m, 1), dtype=torch.int64, device=self.device)[:m] if value is None else value
+        if found is None and with_found:
+            found = torch.empty(max(m, 1), dtype=torch.uint8, device=self.device)[:m]
+        self._check_cmap(t)
+        self._check(probes, value, n_dev, itemsize=8)
+        self._check(found, itemsize=1)
+        if value.dtype != torch.int64 or value.numel() < m or (found is not None and found.numel() < m):
+            raise ValueError("cmap_get: value (int64) and found must hold one entry per probe")
+        self._call("crdt_cmap_lookup", _ref(t), len(t), _ptr(n_dev), _ptr(probes), m, _ptr(value), _ptr(found))
+        return value, found
+
+    def cmap_delta(self, src: CounterMap, dst: CounterMap, n_src_dev: torch.Tensor | None = None,
+                   n_dst_dev: torch.Tensor | None = None, out: CounterMap | None = None,
+                   count: torch.Tensor | None = None, trim: bool = False):
+        """The smallest D with merge(dst, D) == merge(dst, src): the cells of
+        src that dst lacks or holds with a smaller p or n, with src's own p
+        and n.  Returns (D, count) as :meth:`cmap_merge` does, D of capacity
+        len(src)."""
+        out = self._out_cmap(out, len(src), "cmap_delta: out holds fewer cells than src")
+        count = self._cmap_delta(src, dst, n_src_dev, n_dst_dev, out, count)
+        return self._result(trim, count, out, None)
+
+    def cmap_delta_count(self, src: CounterMap, dst: CounterMap, n_src_dev: torch.Tensor | None = None,
+                         n_dst_dev: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(cmap_delta(src, dst)) alone (int64[1] on the device, no
+        synchronisation); 0 iff dst already holds all of src."""
+        return self._cmap_delta(src, dst, n_src_dev, n_dst_dev, None, count)
+
+    def _cmap_delta(self, src: CounterMap, dst: CounterMap, n_src_dev, n_dst_dev, out, count) -> torch.Tensor:
+        count = self._count(count)
+        self._check(count, n_src_dev, n_dst_dev, itemsize=8)
+        self._check_cmap(src, dst, out)
+        self._call("crdt_cmap_delta", _ref(src), len(src), _ptr(n_src_dev), _ref(dst), len(dst), _ptr(n_dst_dev),
+                   _ref(out), count.data_ptr())
+        return count
 
     # -- the causal merge restricted to the key ranges whose digests differ
     #    (crdt_orset_merge_causal_ranges)

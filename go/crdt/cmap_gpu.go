@@ -1,0 +1,75 @@
+//go:build cgo && rocm
+
+// The keyed PN-Counter map on device pointers (crdt_cmap_*, include/crdt_amd.h):
+// the convergent form of the per-key curr + change fold of the reference's
+// replay (main.go:75-98).  A state is cells (key, rep, p, n) strictly ascending
+// by (key, rep) in HBM.  Uncompiled in the build image (no Go toolchain).
+package crdt
+
+/*
+#include "crdt_amd.h"
+*/
+import "C"
+
+// CMapMerge: the join of two counter maps -- the union of their cells, a cell
+// held by both with the unsigned maximum of p and of n -- into out (capacity
+// naMax + nbMax cells; nil: the count alone), its length into countDev.  naDev /
+// nbDev (nil: all nMax cells of the side) chain the call off device counts
+// with no read-back.  Enqueued: crdt_ctx_sync before reading.
+func CMapMerge(a *C.crdt_cmap, naMax int, naDev *C.uint64_t, b *C.crdt_cmap, nbMax int, nbDev *C.uint64_t,
+	out *C.crdt_cmap, countDev *C.uint64_t) error {
+	if a == nil || b == nil || countDev == nil || naMax < 0 || nbMax < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_merge(gpuCtx, a, C.size_t(naMax), naDev, b, C.size_t(nbMax), nbDev, out, countDev))
+}
+
+// CMapApply: replica rep's batch of m increments (opKeyDev strictly ascending)
+// applied to t -- cell (opKey[i], rep) becomes (p + opDp[i], n + opDn[i]) mod
+// 2^64, an absent cell is created from (0, 0) -- into out (capacity nMax + m;
+// nil: the count alone).  The integer AddCommand (main.go:173-207) as a state
+// change that commutes.  Enqueued.
+func CMapApply(t *C.crdt_cmap, nMax int, nDev *C.uint64_t, rep uint32, opKeyDev, opDpDev, opDnDev *C.uint64_t, m int,
+	out *C.crdt_cmap, countDev *C.uint64_t) error {
+	if t == nil || countDev == nil || nMax < 0 || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_apply(gpuCtx, t, C.size_t(nMax), nDev, C.uint32_t(rep), opKeyDev, opDpDev, opDnDev,
+		C.size_t(m), out, countDev))
+}
+
+// CMapValues: one row per distinct key of t, in key order -- the key, P and N
+// (the sums of the key's p and n cells mod 2^64) and value = int64(P - N), the
+// number the replay of main.go:75-98 arrives at -- each output of capacity nMax
+// rows and optional (all nil: the number of distinct keys alone).  Enqueued.
+func CMapValues(t *C.crdt_cmap, nMax int, nDev, keysOutDev, pOutDev, nOutDev *C.uint64_t, valueOutDev *C.int64_t,
+	countDev *C.uint64_t) error {
+	if t == nil || countDev == nil || nMax < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_values(gpuCtx, t, C.size_t(nMax), nDev, keysOutDev, pOutDev, nOutDev, valueOutDev, countDev))
+}
+
+// CMapLookup: the counter of each of the m probe keys (any order, repeats
+// allowed) into valueOutDev, 0 where the key is absent; foundOutDev (may be
+// nil) 1 / 0.  No probes enqueue nothing.
+func CMapLookup(t *C.crdt_cmap, nMax int, nDev, probesDev *C.uint64_t, m int, valueOutDev *C.int64_t,
+	foundOutDev *C.uint8_t) error {
+	if t == nil || nMax < 0 || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_lookup(gpuCtx, t, C.size_t(nMax), nDev, probesDev, C.size_t(m), valueOutDev, foundOutDev))
+}
+
+// CMapDelta: the smallest D with merge(dst, D) == merge(dst, src) -- the cells
+// of src that dst lacks or holds with a smaller p or n, with src's own p and n
+// -- into out (capacity nsMax; nil: the count alone, 0 iff dst already holds
+// all of src).  What a pull needs to ship instead of the entire Diff
+// (main.go:153-170).  Enqueued.
+func CMapDelta(src *C.crdt_cmap, nsMax int, nsDev *C.uint64_t, dst *C.crdt_cmap, ndMax int, ndDev *C.uint64_t,
+	out *C.crdt_cmap, countDev *C.uint64_t) error {
+	if src == nil || dst == nil || countDev == nil || nsMax < 0 || ndMax < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_delta(gpuCtx, src, C.size_t(nsMax), nsDev, dst, C.size_t(ndMax), ndDev, out, countDev))
+}

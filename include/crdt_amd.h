@@ -128,6 +128,65 @@ int crdt_pncounter_join(crdt_ctx *ctx, const uint64_t *pa_dev, const uint64_t *n
 int crdt_pncounter_value(crdt_ctx *ctx, const uint64_t *p_dev, const uint64_t *n_dev,
                          int64_t *out_dev, size_t rows, size_t nodes);
 
+/* ---------------------------------------------- keyed PN-Counter map (cmap)
+ * The sparse form of the counters above: "key k is a number that many replicas
+ * increment concurrently" -- the convergent form of the per-key curr + change
+ * fold of the reference's replay (main.go:75-98), which depends on the log's
+ * order and on every entry arriving once.  Structure-of-arrays cells: replica
+ * rep's increments p and decrements n of key.
+ * A state is STRICTLY ASCENDING by (key, rep), both compared unsigned, each
+ * cell at most once: a precondition of every call below on every side, and a
+ * property of every output.  For an input that breaks it the result is
+ * unspecified, but no kernel reads or writes outside the given lengths and
+ * count <= na + nb still holds.  All arithmetic is modulo 2^64.
+ * Lengths, as for the set ops: n_max is the buffer's length, an optional
+ * n_dev (device uint64, may be NULL) the length on the device; *n_dev > n_max
+ * touches no cell, stores *count_dev = ~0 and raises CRDT_DEV_RANGE; no kernel
+ * reads at or past min(*n_dev, n_max); n_max == 0 launches nothing but the
+ * count store.  Every call is stream-ordered with no host synchronisation;
+ * workspace from the context only (capturable after crdt_ctx_reserve).
+ * CRDT_E_INVAL: a NULL ctx, state or count_dev, NULL fields of a side with a
+ * non-zero length, key / rep / p / n not naturally aligned (8 / 4 / 8 / 8), a
+ * length or count pointer not 8-byte aligned, any output overlapping any input
+ * or another output.  CRDT_E_RANGE: a length >= 2^62 or more tiles than a
+ * launch holds. */
+typedef struct crdt_cmap {
+    uint64_t *key;
+    uint32_t *rep;
+    uint64_t *p;
+    uint64_t *n;
+} crdt_cmap;
+/* The join: the union of the cells; a cell held by both sides gets p = max(p_a,
+ * p_b), n = max(n_a, n_b), unsigned.  out holds >= na_max + nb_max cells;
+ * out == NULL: the count alone. */
+int crdt_cmap_merge(crdt_ctx *ctx, const crdt_cmap *a, size_t na_max, const uint64_t *na_dev,
+                    const crdt_cmap *b, size_t nb_max, const uint64_t *nb_dev,
+                    const crdt_cmap *out, uint64_t *count_dev);
+/* Replica rep's batch of m increments, op_key strictly ascending: cell
+ * (op_key[i], rep) becomes (p + op_dp[i], n + op_dn[i]); an absent cell is
+ * created from (0, 0), also by an op with dp == dn == 0.  out holds >= n_max +
+ * m cells; out == NULL: the count alone. */
+int crdt_cmap_apply(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev, uint32_t rep,
+                    const uint64_t *op_key_dev, const uint64_t *op_dp_dev, const uint64_t *op_dn_dev,
+                    size_t m, const crdt_cmap *out, uint64_t *count_dev);
+/* One row per distinct key, in key order: the key, P = the sum of p and N =
+ * the sum of n over its cells, value = (int64)(P - N).  Every output (n_max
+ * rows each) may be NULL; all NULL: the number of distinct keys alone. */
+int crdt_cmap_values(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev,
+                     uint64_t *keys_out, uint64_t *p_out, uint64_t *n_out, int64_t *value_out,
+                     uint64_t *count_dev);
+/* m probe keys, any order, repeats allowed: value_out[i] = the counter of
+ * probes[i], 0 where the key is absent; found_out (may be NULL) 1 / 0.  A
+ * device length out of range: every value 0, every found 0, CRDT_DEV_RANGE. */
+int crdt_cmap_lookup(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev,
+                     const uint64_t *probes_dev, size_t m, int64_t *value_out, uint8_t *found_out);
+/* The smallest D with merge(dst, D) == merge(dst, src): a cell of src ships,
+ * with src's own p and n, when dst has no such cell, or p_s > p_d, or n_s >
+ * n_d.  out holds >= ns_max cells; out == NULL: the count alone (0: in sync). */
+int crdt_cmap_delta(crdt_ctx *ctx, const crdt_cmap *src, size_t ns_max, const uint64_t *ns_dev,
+                    const crdt_cmap *dst, size_t nd_max, const uint64_t *nd_dev,
+                    const crdt_cmap *out, uint64_t *count_dev);
+
 /* ------------------------------------------- streaming peaks
  * Measurement utilities, no reference counterpart: the bench reports every
  * kernel's fraction of a self-measured copy-kernel peak beside the spec peak.
