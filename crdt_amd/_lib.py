@@ -188,6 +188,8 @@ SIGNATURES = {
     "crdt_cmap_lookup": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, _P, _SZ, _P, _P]),
     "crdt_cmap_delta": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, C.POINTER(crdt_cmap), _SZ, _P, C.POINTER(crdt_cmap),
                              _P]),
+    "crdt_cmap_digest": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, _P, _SZ, _P, _P]),
+    "crdt_cmap_select": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, _P, _SZ, _P, C.POINTER(crdt_cmap), _P]),
     "crdt_vclock_classify": (_I, [_CTX, _P, _P, _P, _SZ, _SZ]),
     "crdt_lww_merge": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, C.POINTER(crdt_tuples), _SZ,
                             C.POINTER(crdt_tuples), _P]),

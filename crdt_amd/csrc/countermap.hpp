@@ -26,11 +26,15 @@
 // One-sided: values = heads (key[i] != key[i - 1]) through the by-position
 // scaffold, then a segmented sum per tile; lookup = one probe per lane, a long
 // key run finished by the whole wave.
+// Range digests (digest, select): by position over tiles of
+// 2048 cells, a wave 8 consecutive 64-cell words, buckets and accumulation
+// digest.hpp's.  Every cell is a deciding position: nothing walks back.
 //
 // No kernel reads a cell at or past min(*n_dev, n_max) of its side or before
 // 0, whatever the cells hold; a length past its n_max touches nothing (the
 // scan stores the count ~0 and raises CRDT_DEV_RANGE).
 #pragma once
+#include "digest.hpp"
 #include "setread.hpp"
 
 namespace crdt {
@@ -510,6 +514,124 @@ __global__ __launch_bounds__(256) void k_cmap_lookup(crdt_cmap T, uint64_t n_max
             if (found) found[i] = hit ? 1 : 0;
         }
     }
+}
+
+// ---------------------------------------------------------------- range digests
+// h(key, rep, p, n) = sm(sm(sm(sm(key) ^ rep) ^ p) ^ n), sm = SplitMix64's output function
+__device__ __forceinline__ uint64_t cm_hash(uint64_t key, uint32_t rep, uint64_t p, uint64_t n) {
+    return splitmix64(splitmix64(splitmix64(splitmix64(key) ^ (uint64_t)rep) ^ p) ^ n);
+}
+
+// hash[b] += the cells' hashes, count[b] += their number, per bucket (both
+// zeroed by k_dig_init ahead of this kernel).  No LDS, no barrier, no waiting
+// between workgroups.
+__global__ __launch_bounds__(RB) void k_cmap_digest(crdt_cmap T, uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                                                    const uint64_t *__restrict__ sp, uint32_t m,
+                                                    uint64_t *__restrict__ hash, uint64_t *__restrict__ count) {
+    uint64_t n;
+    if (!tile_len(n_max, n_dev, &n)) return;
+    const uint64_t tb = (uint64_t)blockIdx.x * RT;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i0 = tb + (uint64_t)wv * (64 * RWW);
+    if (i0 >= n) return;                                 // (wave-uniform; so n > 0 below)
+    uint64_t k[RWW], p[RWW], q[RWW];
+    uint32_t r[RWW];
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {                      // all four columns in flight; indices clamped into [0, n)
+        const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+        const uint64_t a = i < n ? i : n - 1;
+        k[j] = T.key[a];
+        r[j] = T.rep[a];
+        p[j] = T.p[a];
+        q[j] = T.n[a];
+    }
+    uint32_t blo, bhi;
+    dig_wave_buckets(sp, m, k, &blo, &bhi);
+    if (blo == bhi) {                                    // the whole wave in one bucket
+        uint64_t h = 0;
+        uint32_t c = 0;
+#pragma unroll
+        for (int j = 0; j < RWW; ++j) {
+            if (i0 + (uint64_t)j * 64 + lane < n) {
+                h += cm_hash(k[j], r[j], p[j], q[j]);
+                ++c;
+            }
+        }
+        dig_add_wave(h, c, lane, blo, hash, count);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const bool v = i0 + (uint64_t)j * 64 + lane < n;
+        if (__ballot(v) == 0) continue;
+        const uint32_t b = dig_ub(sp, blo, bhi, k[j]);   // (a clamped lane: the last cell's bucket, with nothing to add)
+        dig_add_runs(v ? cm_hash(k[j], r[j], p[j], q[j]) : 0ull, v ? 1u : 0u, lane, b, hash, count);
+    }
+}
+
+// select, count pass: the cells whose bucket is flagged, as the tile's emit
+// words and count.  Only keys, splitters and flags are read.
+template <bool BITS>
+__global__ __launch_bounds__(RB) void k_cmap_sel_count(const uint64_t *__restrict__ key, uint64_t n_max,
+                                                       const uint64_t *__restrict__ n_dev,
+                                                       const uint64_t *__restrict__ sp, uint32_t m,
+                                                       const uint8_t *__restrict__ flags, uint32_t *__restrict__ tcnt,
+                                                       uint64_t *__restrict__ bits) {
+    __shared__ uint32_t s_cnt[RB / 64];
+    uint64_t n;
+    if (!tile_len(n_max, n_dev, &n)) return;
+    const uint64_t t = blockIdx.x, tb = t * RT;
+    if (tb >= n) return;                                 // (uniform; so n > 0 below)
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i0 = tb + (uint64_t)wv * (64 * RWW);
+    uint32_t cnt = 0;
+    uint64_t mine = 0;
+    if (i0 < n) {                                        // (wave-uniform)
+        uint64_t k[RWW];
+#pragma unroll
+        for (int j = 0; j < RWW; ++j) {                  // indices clamped into [0, n)
+            const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+            k[j] = key[i < n ? i : n - 1];
+        }
+        uint32_t blo, bhi;
+        dig_wave_buckets(sp, m, k, &blo, &bhi);
+        const bool one = blo == bhi;
+        const bool f1 = one && flags[blo] != 0;
+#pragma unroll
+        for (int j = 0; j < RWW; ++j) {
+            const bool v = i0 + (uint64_t)j * 64 + lane < n;
+            bool f = f1;
+            if (!one && v) f = flags[dig_ub(sp, blo, bhi, k[j])] != 0;
+            const uint64_t e = __ballot(v && f);
+            cnt += (uint32_t)__popcll(e);
+            if (lane == j) mine = e;
+        }
+    }
+    if (BITS && lane < RWW) bits[t * RNW + (uint64_t)wv * RWW + lane] = mine;
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+#pragma unroll
+        for (int w = 0; w < RB / 64; ++w) c += s_cnt[w];
+        tcnt[t] = c;
+    }
+}
+
+// select, write pass: the four columns of the emitting cells in one kernel
+// (the bitmap and its prefix counts are read once, not once per column)
+__global__ __launch_bounds__(kTileB) void k_cmap_sel_write(crdt_cmap T, uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                                                           const uint64_t *__restrict__ bits,
+                                                           const uint64_t *__restrict__ ic, crdt_cmap out,
+                                                           uint32_t *__restrict__ err) {
+    tile_emit_by_position<false>(n_max, n_dev, bits, ic, err, [&](uint64_t i, uint64_t at, uint8_t) {
+        const uint64_t key = T.key[i], p = T.p[i], q = T.n[i];
+        const uint32_t rp = T.rep[i];
+        out.key[at] = key;
+        out.rep[at] = rp;
+        out.p[at] = p;
+        out.n[at] = q;
+    });
 }
 
 }  // namespace crdt

@@ -1,6 +1,7 @@
 // counters.hip -- dense and keyed counters: the G-Counter / PN-Counter /
 // vector-clock join kernels and the entry points of the keyed
-// PN-Counter map (crdt_cmap_*; kernels in countermap.hpp).
+// PN-Counter map (crdt_cmap_*; kernels in countermap.hpp, DESIGN.md §5.23, its
+// range digests §5.24).
 //
 // No reference code exists for these types: they are the
 // standard state-based CRDT joins (elementwise unsigned max) over a replica
@@ -652,5 +653,77 @@ extern "C" int crdt_cmap_lookup(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max,
     k_cmap_lookup<<<grid_for(m, 256, (unsigned)ctx->num_cus * 8), 256, 0, ctx->stream>>>(*t, n_max, n_dev, probes_dev, m,
                                                                                        value_out, found_out,
                                                                                        ctx->dev_status);
+    return check_launch(ctx);
+}
+
+// what the digest and the selection check alike: t, n_max, the splitters
+static int cmap_dig_check_in(const crdt_cmap *t, size_t n_max, const uint64_t *n_dev, const uint64_t *sp, size_t m) {
+    if (!t) return CRDT_E_INVAL;
+    if (n_max >= (1ULL << 62) || m >= kDigMaxSplit) return CRDT_E_RANGE;
+    if ((m && !sp) || (((uintptr_t)sp | (uintptr_t)n_dev) & 7) != 0) return CRDT_E_INVAL;
+    if ((n_max && cmap_null(t)) || cmap_misaligned(t)) return CRDT_E_INVAL;
+    if ((n_max + RT - 1) / RT >= 0x7fffffffULL) return CRDT_E_RANGE;   // (so no byte count below wraps)
+    return CRDT_OK;
+}
+
+extern "C" int crdt_cmap_digest(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev,
+                                const uint64_t *splitters_dev, size_t m, uint64_t *hash_out_dev,
+                                uint64_t *count_out_dev) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!hash_out_dev || !count_out_dev) return CRDT_E_INVAL;
+    rc = cmap_dig_check_in(t, n_max, n_dev, splitters_dev, m);
+    if (rc) return rc;
+    if ((((uintptr_t)hash_out_dev | (uintptr_t)count_out_dev) & 7) != 0) return CRDT_E_INVAL;
+    {
+        CmSpan in[6], o[2];
+        int ni = cmap_fields(t, n_max, in);
+        in[ni++] = {n_dev, 8};
+        in[ni++] = {splitters_dev, m * 8};
+        o[0] = {hash_out_dev, (m + 1) * 8};
+        o[1] = {count_out_dev, (m + 1) * 8};
+        if (cmap_clash(o, 2, in, ni)) return CRDT_E_INVAL;
+    }
+    const size_t ntiles = (n_max + RT - 1) / RT;
+    dig_init(ctx, n_max, n_dev, m, hash_out_dev, count_out_dev);
+    if (ntiles)
+        k_cmap_digest<<<(unsigned)ntiles, RB, 0, ctx->stream>>>(*t, n_max, n_dev, splitters_dev, (uint32_t)m, hash_out_dev,
+                                                                count_out_dev);
+    return check_launch(ctx);
+}
+
+extern "C" int crdt_cmap_select(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev,
+                                const uint64_t *splitters_dev, size_t m, const uint8_t *flags_dev,
+                                const crdt_cmap *out, uint64_t *count_dev) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!count_dev || !flags_dev) return CRDT_E_INVAL;
+    rc = cmap_dig_check_in(t, n_max, n_dev, splitters_dev, m);
+    if (rc) return rc;
+    if (((uintptr_t)count_dev & 7) != 0 || (out && cmap_misaligned(out))) return CRDT_E_INVAL;
+    if (out && n_max && cmap_null(out)) return CRDT_E_INVAL;
+    {
+        CmSpan in[7], o[5];
+        int ni = cmap_fields(t, n_max, in), no = 0;
+        in[ni++] = {n_dev, 8};
+        in[ni++] = {splitters_dev, m * 8};
+        in[ni++] = {flags_dev, m + 1};
+        if (out) no = cmap_fields(out, n_max, o);
+        o[no++] = {count_dev, 8};
+        if (cmap_clash(o, no, in, ni)) return CRDT_E_INVAL;
+    }
+    const size_t ntiles = (n_max + RT - 1) / RT;
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, false, false, RNW);
+    if (rc) return rc;
+    const bool wr = out != nullptr;
+    const hipStream_t s = ctx->stream;
+    const unsigned g = (unsigned)ntiles;
+    if (ntiles) {
+        if (wr) k_cmap_sel_count<true><<<g, RB, 0, s>>>(t->key, n_max, n_dev, splitters_dev, (uint32_t)m, flags_dev, w.tcnt, w.bits);
+        else k_cmap_sel_count<false><<<g, RB, 0, s>>>(t->key, n_max, n_dev, splitters_dev, (uint32_t)m, flags_dev, w.tcnt, w.bits);
+    }
+    w.scan<NoCarry<>>(ctx, n_max, n_dev, 0, nullptr, wr, count_dev);
+    if (ntiles && wr) k_cmap_sel_write<<<g, kTileB, 0, s>>>(*t, n_max, n_dev, w.bits, w.ic, *out, ctx->dev_status);
     return check_launch(ctx);
 }

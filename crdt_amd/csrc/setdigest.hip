@@ -35,16 +35,10 @@
 //            only over its own copies: the work is linear in n however many
 //            tiles one tag spans, and no workgroup waits on another -- no
 //            carry, no look-back, no flags.
-//   bucket : the wave searches the splitters for its first and last key
-//            (uniform loads); when both fall into one bucket, the common case,
-//            no lane searches.  Otherwise each lane searches between the two.
-//            Every search is an upper bound inside [0, m], whatever the
-//            splitters hold: unsorted splitters give unspecified digests, never
-//            an access out of range.
-//   digest : hashes at the deciding positions, a reduction within the wave over
-//            runs of equal bucket (one run per wave in the common case, else a
-//            segmented shuffle scan per word), one 64-bit global atomicAdd pair
-//            per wave (word) and bucket run.
+//   bucket, digest : digest.hpp's, shared with the counter map's digest -- the
+//            wave's bucket range from its first and last key, hashes at the
+//            deciding positions, one atomicAdd pair per wave (word) and bucket
+//            run.
 //   select : compaction with another drop predicate (the bucket is unflagged):
 //            count (emit / tomb bitmaps and tile counts), then the scan and the
 //            write pass of settile.hpp: k_tile_scan<NoCarry> -- the tomb is
@@ -56,26 +50,14 @@
 // tuple and raises CRDT_DEV_RANGE (digest: every entry of both outputs ~0;
 // select: a count of ~0).  No kernel reads a tuple at or past that length or
 // before 0, a splitter at or past m, or a flag at or past m + 1.
-#include "settile.hpp"
+#include "digest.hpp"
 
 namespace crdt {
 
 constexpr int GT = kTile, GB = kTileB, GWW = kTileWW, GNW = kTileNW;   // tile, its threads, words per wave and tile
-constexpr size_t kDigMaxSplit = (size_t)1 << 24;
 
 __device__ __forceinline__ uint64_t dig_hash(uint64_t key, uint64_t ts, uint32_t rep, uint32_t tomb) {
     return splitmix64(splitmix64(splitmix64(key) ^ ts) ^ (((uint64_t)rep << 1) | (uint64_t)(tomb & 1u)));
-}
-
-// lo + #{ j in [lo, hi) : sp[j] <= key } for ascending sp; always a value in
-// [lo, max(lo, hi)], and only sp[lo .. hi) is read
-__device__ __forceinline__ uint32_t dig_ub(const uint64_t *__restrict__ sp, uint32_t lo, uint32_t hi, uint64_t key) {
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (sp[mid] <= key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // The canonical tuples of one wave's 8 words from i0 on (i0 < n).  Per lane a
@@ -179,31 +161,7 @@ __device__ __forceinline__ void dig_decide(const crdt_tuples &T, uint64_t n, uin
     *dead_out = dead;
 }
 
-// The bucket range of the wave's keys: [*blo, *bhi] from its first and its
-// last (clamped) key, both wave-uniform.
-__device__ __forceinline__ void dig_wave_buckets(const uint64_t *__restrict__ sp, uint32_t m, const uint64_t (&k)[GWW],
-                                                 uint32_t *blo, uint32_t *bhi) {
-    const uint64_t kf = (uint64_t)__shfl((unsigned long long)k[0], 0, 64);
-    const uint64_t kl = (uint64_t)__shfl((unsigned long long)k[GWW - 1], 63, 64);
-    *blo = __builtin_amdgcn_readfirstlane(dig_ub(sp, 0, m, kf));
-    *bhi = __builtin_amdgcn_readfirstlane(dig_ub(sp, 0, m, kl));
-}
-
 // ---------------------------------------------------------------- digest
-// hash / count [0 .. m1) zeroed, or poisoned when the device count is out of range
-__global__ __launch_bounds__(256) void k_dig_init(uint64_t n_max, const uint64_t *__restrict__ n_dev, uint64_t m1,
-                                                  uint64_t *__restrict__ hash, uint64_t *__restrict__ count,
-                                                  uint32_t *__restrict__ err) {
-    uint64_t n;
-    const bool ok = tile_len(n_max, n_dev, &n);
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < m1) {
-        hash[i] = ok ? 0ull : ~0ull;
-        count[i] = ok ? 0ull : ~0ull;
-    }
-    if (!ok && i == 0) atomicOr(err, CRDT_DEV_RANGE);
-}
-
 template <bool LWW>
 __global__ __launch_bounds__(GB) void k_dig_digest(crdt_tuples T, uint64_t n_max, const uint64_t *__restrict__ n_dev,
                                                    const uint64_t *__restrict__ sp, uint32_t m,
@@ -219,7 +177,6 @@ __global__ __launch_bounds__(GB) void k_dig_digest(crdt_tuples T, uint64_t n_max
     dig_decide<LWW>(T, n, i0, lane, k, ts, r, &dec, &dead);
     uint32_t blo, bhi;
     dig_wave_buckets(sp, m, k, &blo, &bhi);
-    unsigned long long *const H = (unsigned long long *)hash, *const C = (unsigned long long *)count;
     if (blo == bhi) {                                        // the whole wave in one bucket
         uint64_t h = 0;
         uint32_t c = 0;
@@ -230,15 +187,7 @@ __global__ __launch_bounds__(GB) void k_dig_digest(crdt_tuples T, uint64_t n_max
                 ++c;
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            h += (uint64_t)__shfl_down((unsigned long long)h, o, 64);
-            c += __shfl_down(c, o, 64);
-        }
-        if (lane == 0 && c != 0) {
-            atomicAdd(H + blo, (unsigned long long)h);
-            atomicAdd(C + blo, (unsigned long long)c);
-        }
+        dig_add_wave(h, c, lane, blo, hash, count);
         return;
     }
 #pragma unroll
@@ -248,24 +197,7 @@ __global__ __launch_bounds__(GB) void k_dig_digest(crdt_tuples T, uint64_t n_max
         const uint32_t b = dig_ub(sp, blo, bhi, k[j]);
         uint64_t h = d ? dig_hash(k[j], ts[j], r[j], (dead >> j) & 1) : 0ull;
         uint32_t c = d ? 1u : 0u;
-        // runs of equal bucket: a segmented inclusive scan, the run's last lane adds
-        const uint32_t bp = __shfl_up(b, 1, 64);
-        const uint64_t HD = __ballot(lane == 0 || b != bp);
-        const int seg = 63 - __builtin_clzll(HD & ((2ull << lane) - 1));
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t yh = (uint64_t)__shfl_up((unsigned long long)h, o, 64);
-            const uint32_t yc = __shfl_up(c, o, 64);
-            if (lane - o >= seg) {
-                h += yh;
-                c += yc;
-            }
-        }
-        const bool tail = lane == 63 || ((HD >> (lane + 1)) & 1);
-        if (tail && c != 0) {
-            atomicAdd(H + b, (unsigned long long)h);
-            atomicAdd(C + b, (unsigned long long)c);
-        }
+        dig_add_runs(h, c, lane, b, hash, count);
     }
 }
 
@@ -377,8 +309,7 @@ extern "C" int crdt_set_digest(crdt_ctx *ctx, int mode, const crdt_tuples *t, si
     }
     const hipStream_t s = ctx->stream;
     const size_t ntiles = (n_max + GT - 1) / GT;
-    k_dig_init<<<(unsigned)((m + 1 + 255) / 256), 256, 0, s>>>(n_max, n_dev, m + 1, hash_out_dev, count_out_dev,
-                                                               ctx->dev_status);
+    dig_init(ctx, n_max, n_dev, m, hash_out_dev, count_out_dev);
     if (ntiles) {
         const unsigned g = (unsigned)ntiles;
         if (mode == CRDT_SET_LWW)

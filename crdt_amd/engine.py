@@ -956,6 +956,64 @@ class Engine:
                    _ref(out), count.data_ptr())
         return count
 
+    # -- range digests of a counter map: where two replicas that share no memory
+    #    differ (crdt_cmap_digest / crdt_cmap_select; the diff is digest_diff)
+    def cmap_digest(self, t: CounterMap, splitters: torch.Tensor | None, n_dev: torch.Tensor | None = None,
+                    hash_out: torch.Tensor | None = None, count_out: torch.Tensor | None = None):
+        """One order-independent fingerprint per key range of the counter map
+        ``t``: returns (hash, count), int64 storage of uint64 on the device,
+        len(splitters) + 1 entries each, no synchronisation.  The buckets are
+        :meth:`set_digest`'s (``splitters`` ascending uint64 in int64 storage
+        on the device; None or empty: one bucket; all cells of a key share a
+        bucket); hash[b] is the wrapping sum over the cells in b of
+        sm(sm(sm(sm(key) ^ rep) ^ p) ^ n), sm =
+        :func:`crdt_amd.synth.splitmix64`, count[b] their number.  ``n_dev``
+        as in :meth:`cmap_merge`; a value over len(t) leaves every entry
+        2^64 - 1 and raises CRDT_DEV_RANGE."""
+        m = 0 if splitters is None else splitters.numel()
+        hash_out = torch.empty(m + 1, dtype=torch.int64, device=self.device) if hash_out is None else hash_out
+        count_out = torch.empty(m + 1, dtype=torch.int64, device=self.device) if count_out is None else count_out
+        self._check_cmap(t)
+        self._check(hash_out, count_out, itemsize=8)
+        if hash_out.numel() < m + 1 or count_out.numel() < m + 1:
+            raise ValueError("cmap_digest: the outputs must hold len(splitters) + 1 entries")
+        self._check(splitters, n_dev, itemsize=8)
+        self._call("crdt_cmap_digest", _ref(t), len(t), _ptr(n_dev), _ptr(splitters) if m else None, m,
+                   hash_out.data_ptr(), count_out.data_ptr())
+        return hash_out, count_out
+
+    def cmap_select(self, t: CounterMap, splitters: torch.Tensor | None, flags: torch.Tensor,
+                    n_dev: torch.Tensor | None = None, out: CounterMap | None = None,
+                    count: torch.Tensor | None = None, trim: bool = False):
+        """The cells of ``t`` whose key falls into a bucket with ``flags[b] !=
+        0`` (uint8[len(splitters) + 1], e.g. :meth:`digest_diff`'s), in order
+        and unchanged: what a replica ships for the differing ranges.  The
+        merge is monotone, so the receiver's side is ``cmap_merge(dst, out,
+        n_b_dev=count)``.  Returns (out, count) as :meth:`cmap_delta` does,
+        out of capacity len(t)."""
+        out = self._out_cmap(out, len(t), "cmap_select: out holds fewer cells than t")
+        count = self._cmap_select(t, splitters, flags, n_dev, out, count)
+        return self._result(trim, count, out, None)
+
+    def cmap_select_count(self, t: CounterMap, splitters: torch.Tensor | None, flags: torch.Tensor,
+                          n_dev: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(:meth:`cmap_select`) alone (int64[1] on the device, no
+        synchronisation): how much the flagged ranges would ship."""
+        return self._cmap_select(t, splitters, flags, n_dev, None, count)
+
+    def _cmap_select(self, t: CounterMap, splitters, flags, n_dev, out, count) -> torch.Tensor:
+        count = self._count(count)
+        m = 0 if splitters is None else splitters.numel()
+        self._check(count, itemsize=8)
+        self._check(flags, itemsize=1)
+        if flags.numel() < m + 1:
+            raise ValueError("cmap_select: flags must hold len(splitters) + 1 entries")
+        self._check_cmap(t, out)
+        self._check(splitters, n_dev, itemsize=8)
+        self._call("crdt_cmap_select", _ref(t), len(t), _ptr(n_dev), _ptr(splitters) if m else None, m, _ptr(flags),
+                   _ref(out), count.data_ptr())
+        return count
+
     # -- the causal merge restricted to the key ranges whose digests differ
     #    (crdt_orset_merge_causal_ranges)
     def causal_merge_ranges(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet, ctx_b: torch.Tensor | None,
@@ -1038,11 +1096,13 @@ class Engine:
         return hash_out, count_out
 
     def digest_diff(self, da, db, flags: torch.Tensor | None = None, n_diff: torch.Tensor | None = None):
-        """Which buckets of two :meth:`set_digest` results (hash, count)
-        differ: returns (flags, n_diff) -- uint8[buckets], 1 where the hashes
-        or the counts differ or either digest is poisoned, and their number
-        (int64[1]), on the device, no synchronisation.  The digests may come
-        from another replica; both must be over the same splitters."""
+        """Which buckets of two :meth:`set_digest` -- or two
+        :meth:`cmap_digest` -- results (hash, count) differ: returns (flags,
+        n_diff) -- uint8[buckets], 1 where the hashes or the counts differ or
+        either digest is poisoned, and their number (int64[1]), on the device,
+        no synchronisation.  It compares plain arrays, so it serves both
+        digests.  The digests may come from another replica; both must be of
+        one state type and over the same splitters."""
         (ha, ca), (hb, cb) = da, db
         nb = ha.numel()
         if not (ca.numel() == hb.numel() == cb.numel() == nb):

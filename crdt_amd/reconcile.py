@@ -1,4 +1,5 @@
-"""Range-based reconciliation of two set replicas.
+"""Range-based reconciliation of two replicas of a keyed state type
+(sets: DESIGN.md §5.16; counter maps: §5.24).
 
 Two replicas that do not share a memory learn where they differ from small
 per-range fingerprints instead of each other's state: both cut the key space
@@ -9,6 +10,9 @@ buckets that differ (:meth:`Engine.digest_diff`) and ship only those
 Diff every round (main.go:153-170, :245-256).  :func:`causal_round` is the
 same round for the tombstone-free OR-Set, whose merge is not monotone and
 needs the buckets along (:meth:`Engine.causal_merge_ranges`).
+:func:`cmap_round` is the round for the keyed PN-Counter map
+(:meth:`Engine.cmap_digest`, :meth:`Engine.cmap_select`), whose merge is
+monotone and takes the selection as it is.
 
 Everything here runs in the library's HIP kernels; torch allocates, indexes
 the splitter keys and fills buffers.
@@ -17,15 +21,18 @@ from __future__ import annotations
 
 import torch
 
-from .engine import Engine, TupleSet
+from .engine import CounterMap, Engine, TupleSet
 
 
-def key_splitters(t: TupleSet, m: int) -> torch.Tensor:
+def key_splitters(t: TupleSet | CounterMap, m: int) -> torch.Tensor:
     """``m`` splitters for about equally filled buckets of the sorted state
-    ``t``: every ceil(n / (m + 1))-th key, t.key[step], t.key[2 step], ...
+    ``t`` (a set state or a counter map: anything with ``.key`` and a
+    length): every ceil(n / (m + 1))-th key, t.key[step], t.key[2 step], ...
     (indices past the end take the last key; duplicates are allowed and give
-    empty buckets).  An int64-storage device tensor, ascending as unsigned
-    because t is sorted.  An empty ``t`` gives all-zero splitters."""
+    empty buckets).  A counter map repeats a key once per replica cell, so a
+    key with many cells is drawn more than once and some buckets come out
+    empty.  An int64-storage device tensor, ascending as unsigned because t is
+    sorted.  An empty ``t`` gives all-zero splitters."""
     if m < 0:
         raise ValueError("key_splitters: m must be >= 0")
     n = len(t)
@@ -138,3 +145,36 @@ def causal_round(eng: Engine, A: TupleSet, ctx_a: torch.Tensor | None, B: TupleS
     ma, ctx_ma, ca = eng.causal_merge_ranges(A, ctx_a, sel_b, ctx_b, splitters, flags, n_b_dev=ship_b)
     mb, ctx_mb, cb = eng.causal_merge_ranges(B, ctx_b, sel_a, ctx_a, splitters, flags, n_b_dev=ship_a)
     return (ma, ca, ctx_ma), (mb, cb, ctx_mb), flags, (ship_a, ship_b)
+
+
+def cmap_round(eng: Engine, A: CounterMap, B: CounterMap, splitters: torch.Tensor | None):
+    """One reconciliation round between the counter maps ``A`` and ``B``
+    (DESIGN.md §5.24), both on ``eng``'s device, standing in for two replicas:
+    each side's :meth:`Engine.cmap_digest` over ``splitters``, the diff of the
+    two, each side's :meth:`Engine.cmap_select` of the flagged buckets, and
+    ``cmap_merge(A, sel(B))`` / ``cmap_merge(B, sel(A))``.  The merge is
+    monotone and takes its sides' lengths from the device, so each selection
+    goes in as it is with its device count as ``n_b_dev``.  Everything is
+    enqueued on the stream with no synchronisation and no read-back.
+
+    Returns ``((MA, ca), (MB, cb), flags, (ship_a, ship_b))``: the merged
+    maps (CounterMaps of capacity len(A) + len(B), their first ``ca`` /
+    ``cb`` cells valid, int64[1] device counts), the uint8 flags of the
+    buckets that differed, and the numbers of cells A and B had to ship
+    (int64[1] on the device).  MA and MB both equal ``cmap_merge(A, B)`` with
+    probability about 1 - 2^-64 per differing bucket; the digest is a
+    checksum, not a defence against an adversary.
+
+    What crosses the wire between real replicas is the digests (16 bytes a
+    bucket) and the selections (28 bytes a cell).  Recursion with finer
+    splitters inside the flagged ranges works as for :func:`reconcile_round`.
+    """
+    da = eng.cmap_digest(A, splitters)
+    db = eng.cmap_digest(B, splitters)
+    flags, _ = eng.digest_diff(da, db)
+    sel_a, ship_a = eng.cmap_select(A, splitters, flags)
+    sel_b, ship_b = eng.cmap_select(B, splitters, flags)
+    sel_a, sel_b = sel_a.slice(len(A)), sel_b.slice(len(B))      # (an empty map's buffer holds one slot)
+    ma, ca = eng.cmap_merge(A, sel_b, n_b_dev=ship_b)
+    mb, cb = eng.cmap_merge(B, sel_a, n_b_dev=ship_a)
+    return (ma, ca), (mb, cb), flags, (ship_a, ship_b)

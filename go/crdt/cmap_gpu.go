@@ -3,7 +3,8 @@
 // The keyed PN-Counter map on device pointers (crdt_cmap_*, include/crdt_amd.h):
 // the convergent form of the per-key curr + change fold of the reference's
 // replay (main.go:75-98).  A state is cells (key, rep, p, n) strictly ascending
-// by (key, rep) in HBM.  Uncompiled in the build image (no Go toolchain).
+// by (key, rep) in HBM; CMapDigest / CMapSelect are its range digests for
+// replicas that share no memory.  Uncompiled in the build image (no Go toolchain).
 package crdt
 
 /*
@@ -72,4 +73,31 @@ func CMapDelta(src *C.crdt_cmap, nsMax int, nsDev *C.uint64_t, dst *C.crdt_cmap,
 		return status(C.CRDT_E_INVAL)
 	}
 	return status(C.crdt_cmap_delta(gpuCtx, src, C.size_t(nsMax), nsDev, dst, C.size_t(ndMax), ndDev, out, countDev))
+}
+
+// CMapDigest: one order-independent fingerprint per key range of t into
+// hashOutDev / countOutDev, m + 1 entries each -- the buckets are SetDigest's
+// (bucket(key) = #{ j : splitters[j] <= key }, unsigned), hash[b] the wrapping
+// sum over the cells in b of sm(sm(sm(sm(key) ^ rep) ^ p) ^ n), count[b] their
+// number.  Two replicas exchange these 16 bytes a bucket instead of the entire
+// Diff of a gossip pull (main.go:153-170, :245-256); SetDigestDiff flags the
+// buckets that differ.  Enqueued.
+func CMapDigest(t *C.crdt_cmap, nMax int, nDev, splittersDev *C.uint64_t, m int,
+	hashOutDev, countOutDev *C.uint64_t) error {
+	if t == nil || hashOutDev == nil || countOutDev == nil || nMax < 0 || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_digest(gpuCtx, t, C.size_t(nMax), nDev, splittersDev, C.size_t(m), hashOutDev, countOutDev))
+}
+
+// CMapSelect: the cells of t whose bucket has flagsDev[b] != 0 (m + 1 flags),
+// in order and unchanged, into out (capacity nMax; nil: the count alone), their
+// number into countDev: what a replica ships for the differing ranges.  The
+// receiver's side is CMapMerge(dst, out) with countDev as nbDev.  Enqueued.
+func CMapSelect(t *C.crdt_cmap, nMax int, nDev, splittersDev *C.uint64_t, m int, flagsDev *C.uint8_t,
+	out *C.crdt_cmap, countDev *C.uint64_t) error {
+	if t == nil || flagsDev == nil || countDev == nil || nMax < 0 || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_select(gpuCtx, t, C.size_t(nMax), nDev, splittersDev, C.size_t(m), flagsDev, out, countDev))
 }

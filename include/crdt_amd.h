@@ -187,6 +187,39 @@ int crdt_cmap_delta(crdt_ctx *ctx, const crdt_cmap *src, size_t ns_max, const ui
                     const crdt_cmap *dst, size_t nd_max, const uint64_t *nd_dev,
                     const crdt_cmap *out, uint64_t *count_dev);
 
+/* Range digests of a counter map, for anti-entropy between replicas that share
+ * no memory: both cut the key space with the same m ascending splitters,
+ * bucket(key) = #{ j : splitters[j] <= key } compared unsigned (crdt_set_digest's
+ * buckets: m + 1 of them, equal neighbouring splitters give empty ones, all
+ * cells of one key share a bucket), fingerprint their cells per bucket,
+ * exchange the fingerprints (16 bytes a bucket), flag the buckets that differ
+ * with crdt_set_digest_diff -- it compares plain hash[] / count[] arrays and
+ * serves both digests -- and ship crdt_cmap_select's cells alone.  The merge
+ * is monotone, so crdt_cmap_merge(dst, selection) is the whole of the
+ * receiver's side.  With sm = SplitMix64's output function
+ *   h(key, rep, p, n) = sm( sm( sm( sm(key) ^ (uint64)rep ) ^ p ) ^ n ),
+ * hash[b] is the sum mod 2^64 of h over the cells in bucket b and count[b]
+ * their number, bit-exact whatever the order of the adds.
+ * crdt_cmap_digest writes all m + 1 entries of both outputs (n_max == 0 zeroes
+ * them); it needs no workspace.  *n_dev > n_max touches no cell, stores ~0 in
+ * every entry of both outputs and raises CRDT_DEV_RANGE.  Every search stays
+ * inside [0, m] whatever the splitters hold: unsorted splitters give
+ * unspecified digests, never an access outside the splitter, flag or cell
+ * arrays, and every cell still lands in exactly one bucket.
+ * CRDT_E_INVAL beyond the family's: NULL outputs or flags, m != 0 with NULL
+ * splitters, a splitter or output pointer not 8-byte aligned.  CRDT_E_RANGE
+ * beyond the family's: m >= 2^24. */
+int crdt_cmap_digest(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev,
+                     const uint64_t *splitters_dev, size_t m,
+                     uint64_t *hash_out_dev, uint64_t *count_out_dev);          /* m + 1 entries each */
+/* The cells of t whose bucket has flags[b] != 0 (m + 1 flags, e.g.
+ * crdt_set_digest_diff's), in order, all four fields unchanged, into out,
+ * their number to *count_dev.  out holds >= n_max cells; out == NULL: the
+ * count alone. */
+int crdt_cmap_select(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev,
+                     const uint64_t *splitters_dev, size_t m, const uint8_t *flags_dev, /* m + 1 */
+                     const crdt_cmap *out, uint64_t *count_dev);                /* out >= n_max cells; NULL: count alone */
+
 /* ------------------------------------------- streaming peaks
  * Measurement utilities, no reference counterpart: the bench reports every
  * kernel's fraction of a self-measured copy-kernel peak beside the spec peak.
