@@ -190,6 +190,10 @@ SIGNATURES = {
                              _P]),
     "crdt_cmap_digest": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, _P, _SZ, _P, _P]),
     "crdt_cmap_select": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, _P, _SZ, _P, C.POINTER(crdt_cmap), _P]),
+    "crdt_cmap_combine": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, _P, _SZ, C.POINTER(crdt_cmap), _P]),
+    "crdt_cmap_add": (_I, [_CTX, C.POINTER(crdt_cmap), _SZ, _P, C.POINTER(crdt_cmap), _SZ, _P, C.POINTER(crdt_cmap),
+                           _P]),
+    "crdt_cmap_from_ops": (_I, [_CTX, _P, _P, _P, _P, _SZ, C.POINTER(crdt_cmap), _P]),
     "crdt_vclock_classify": (_I, [_CTX, _P, _P, _P, _SZ, _SZ]),
     "crdt_lww_merge": (_I, [_CTX, C.POINTER(crdt_tuples), _SZ, C.POINTER(crdt_tuples), _SZ,
                             C.POINTER(crdt_tuples), _P]),

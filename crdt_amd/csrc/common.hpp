@@ -207,6 +207,8 @@ inline int check_launch(crdt_ctx *ctx) {
 // Grow the workspace to at least `bytes` (synchronises the stream first so
 // that in-flight kernels never see the old buffer freed).
 int ws_reserve(crdt_ctx *ctx, size_t bytes);
+// sort.hip: the bytes crdt_tuples_sort takes from the start of the workspace for n tuples
+size_t tuples_sort_ws_bytes(size_t n);
 // Diagnostic build, "ctx.ws_fill" >= 0: that byte over a scratch arena, on the
 // context's stream (ws_reserve and shard.hip's scratch_reserve on growth,
 // crdt_ctx_reserve and crdt_shard_sync over the whole arena).  The product

@@ -26,6 +26,11 @@
 // One-sided: values = heads (key[i] != key[i - 1]) through the by-position
 // scaffold, then a segmented sum per tile; lookup = one probe per lane, a long
 // key run finished by the whole wave.
+// Combine (crdt_cmap_combine, the back end of crdt_cmap_from_ops; DESIGN.md
+// §5.25): cells ascending by (key, rep) with repeats -> one cell per run, values'
+// scaffold with a head at every change of (key, rep), the key columns written
+// by the sums pass, the amounts optionally gathered through an index column.
+// The additive join (crdt_cmap_add) is merge's passes with the CmAdd policy.
 // Range digests (digest, select): by position over tiles of
 // 2048 cells, a wave 8 consecutive 64-cell words, buckets and accumulation
 // digest.hpp's.  Every cell is a deciding position: nothing walks back.
@@ -453,6 +458,258 @@ __global__ __launch_bounds__(RB) void k_cmap_sums(const uint64_t *__restrict__ p
         }
     }
     if (bad) atomicOr(err, CRDT_DEV_RANGE);
+}
+
+// ---------------------------------------------------------------- combine (crdt_cmap_combine)
+// Sorted cells with repeats -> one cell per distinct (key, rep), p and n summed
+// over the run: values' by-position scaffold with a head at every change of
+// (key, rep).  R: the rep column's element (uint32_t; uint64_t for the sorted
+// view of crdt_cmap_from_ops, whose ts column holds rep widened).
+//
+// Heads: a cell's predecessor comes from the lane below (the word before for
+// lane 0); each wave's first cell looks back once in global memory, in both
+// columns (four look-backs a tile, the first of them across the tile edge).
+template <bool BITS, class R>
+__global__ __launch_bounds__(RB) void k_cmap_cheads(const uint64_t *__restrict__ key, const R *__restrict__ rep,
+                                                    uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                                                    uint32_t *__restrict__ tcnt, uint64_t *__restrict__ bits) {
+    __shared__ uint32_t s_cnt[RB / 64];
+    uint64_t n;
+    if (!tile_len(n_max, n_dev, &n)) return;
+    const uint64_t t = blockIdx.x, tb = t * RT;
+    if (tb >= n) return;                                 // (uniform; so n > 0 below)
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t i0 = tb + (uint64_t)wv * (64 * RWW);
+    uint64_t k[RWW];
+    R r[RWW];
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {                      // indices clamped into [0, n)
+        const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+        const uint64_t a = i < n ? i : n - 1;
+        k[j] = key[a];
+        r[j] = rep[a];
+    }
+    const uint64_t b = i0 > 0 ? (i0 - 1 < n ? i0 - 1 : n - 1) : 0;   // the cell before the wave's first (uniform)
+    uint64_t ck = key[b];
+    R cr = rep[b];
+    uint32_t cnt = 0;
+    uint64_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+        uint64_t kp = (uint64_t)__shfl_up((unsigned long long)k[j], 1, 64);
+        R rp = __shfl_up(r[j], 1, 64);
+        if (lane == 0) {
+            kp = ck;
+            rp = cr;
+        }
+        const uint64_t e = __ballot(i < n && (i == 0 || k[j] != kp || r[j] != rp));
+        cnt += (uint32_t)__popcll(e);
+        if (lane == j) mine = e;
+        ck = (uint64_t)__shfl((unsigned long long)k[j], 63, 64);
+        cr = __shfl(r[j], 63, 64);
+    }
+    if (BITS && lane < RWW) bits[t * RNW + (uint64_t)wv * RWW + lane] = mine;
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+#pragma unroll
+        for (int w = 0; w < RB / 64; ++w) c += s_cnt[w];
+        tcnt[t] = c;
+    }
+}
+
+// k_cmap_sums' pass over two policies (k_cmap_sums itself is kept as it was
+// written: through the policies the compiler schedules its loads differently,
+// and crdt_cmap_values' code objects are not to change).  Src: where cell i's
+// (p, n) come from -- load() fills the wave's RWW words, zeros at and past n,
+// and answers whether a contribution had to be refused.  Sink: where a run
+// piece's sums go (plain() / atomic()) and what is stored at each head cell
+// beside them (head(i, row): the row's key columns).
+struct CmSrcDirect {                                     // cell i contributes p[i], q[i]
+    const uint64_t *__restrict__ p, *__restrict__ q;
+    __device__ __forceinline__ bool load(uint64_t tb, int wv, int lane, uint64_t n, uint64_t *xp, uint64_t *xn) const {
+#pragma unroll
+        for (int j = 0; j < RWW; ++j) {
+            const uint64_t i = tb + (uint64_t)(wv * RWW + j) * 64 + lane;
+            xp[j] = i < n ? p[i] : 0;
+            xn[j] = i < n ? q[i] : 0;
+        }
+        return false;
+    }
+};
+template <class Src, class Sink>
+__device__ __forceinline__ void cmap_sums_tile(const Src &src, uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                                               const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
+                                               const Sink &sink, uint32_t *__restrict__ err, uint64_t *s_tp,
+                                               uint64_t *s_tn) {
+    uint64_t n;
+    if (!tile_len(n_max, n_dev, &n)) return;
+    const uint64_t t = blockIdx.x, tb = t * RT;
+    if (tb >= n) return;                                 // (uniform)
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint64_t xp[RWW], xn[RWW];
+    bool bad = src.load(tb, wv, lane, n, xp, xn);
+    // every wave holds the tile's head words, lane w word w, and the heads before each word
+    const uint64_t wd = lane < RNW ? bits[t * RNW + lane] : 0ull;
+    // the cell after the tile starts a key (the end of the state counts as one)
+    const bool nh = tb + RT < n ? (bits[(t + 1) * RNW] & 1) != 0 : true;
+    const uint32_t pc = (uint32_t)__popcll(wd);
+    uint32_t hx = pc;
+#pragma unroll
+    for (int o = 1; o < RNW; o <<= 1) {
+        const uint32_t y = __shfl_up(hx, o, 64);
+        if (lane >= o) hx += y;
+    }
+    hx -= pc;
+    const uint64_t hm = __ballot(wd != 0);               // bit w: word w holds a head
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const int w = wv * RWW + j;
+        const uint64_t H = (uint64_t)__shfl((unsigned long long)wd, w, 64);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t yp = (uint64_t)__shfl_up((unsigned long long)xp[j], o, 64);
+            const uint64_t yn = (uint64_t)__shfl_up((unsigned long long)xn[j], o, 64);
+            // no head in (lane - o, lane]: the cell o back is of this cell's run
+            if (lane >= o && ((H >> (lane - o + 1)) & ((1ull << o) - 1)) == 0) {
+                xp[j] += yp;
+                xn[j] += yn;
+            }
+        }
+        if (lane == 63) {
+            s_tp[w] = xp[j];
+            s_tn[w] = xn[j];
+        }
+    }
+    __syncthreads();
+    const uint64_t base = ic[t];
+    // What the words before word w leave open, lane w: the tails back to the nearest word with a head, that
+    // word's included -- one segmented scan of the 32 tails per wave (a word with a head starts a segment),
+    // then one lane up.
+    uint64_t cpl = lane < RNW ? s_tp[lane] : 0ull, cnl = lane < RNW ? s_tn[lane] : 0ull;
+#pragma unroll
+    for (int o = 1; o < RNW; o <<= 1) {
+        const uint64_t yp = (uint64_t)__shfl_up((unsigned long long)cpl, o, 64);
+        const uint64_t yn = (uint64_t)__shfl_up((unsigned long long)cnl, o, 64);
+        if (lane >= o && ((hm >> (lane - o + 1)) & ((1ull << o) - 1)) == 0) {
+            cpl += yp;
+            cnl += yn;
+        }
+    }
+    cpl = (uint64_t)__shfl_up((unsigned long long)cpl, 1, 64);
+    cnl = (uint64_t)__shfl_up((unsigned long long)cnl, 1, 64);
+    if (lane == 0) cpl = cnl = 0;
+#pragma unroll
+    for (int j = 0; j < RWW; ++j) {
+        const int w = wv * RWW + j;
+        const uint64_t i = tb + (uint64_t)w * 64 + lane;
+        const uint64_t H = (uint64_t)__shfl((unsigned long long)wd, w, 64);
+        const uint32_t hb = __shfl(hx, w, 64);
+        const uint64_t Hn = w + 1 < RNW ? (uint64_t)__shfl((unsigned long long)wd, (w + 1) & (RNW - 1), 64) : 0ull;
+        const uint64_t cp = (uint64_t)__shfl((unsigned long long)cpl, w, 64);
+        const uint64_t cn = (uint64_t)__shfl((unsigned long long)cnl, w, 64);
+        const uint64_t upto = (2ull << lane) - 1;        // bits 0 .. lane
+        const bool last = w == RNW - 1 && lane == 63;    // the tile's last cell
+        const bool nxt = lane < 63 ? ((H >> (lane + 1)) & 1) != 0 : (last ? nh : (Hn & 1) != 0);
+        if (i < n && ((H >> lane) & 1)) {                // a head: its row is the run's
+            const uint64_t hrow = base + hb + (uint32_t)__popcll(H & upto) - 1;
+            if (hrow < n_max) sink.head(i, hrow);
+            else bad = true;
+        }
+        if (!(i < n && (i + 1 >= n || nxt || last))) continue;   // the last cell of a run piece
+        const bool open = (H & upto) == 0;               // the piece began before this word
+        const uint32_t heads = hb + (uint32_t)__popcll(H & upto);   // the tile's heads up to this cell
+        const uint64_t sp = xp[j] + (open ? cp : 0), sn = xn[j] + (open ? cn : 0);
+        const uint64_t row = base + heads - 1;
+        if (base + heads == 0 || row >= n_max) {         // (the bitmaps of this call's heads pass never do this)
+            bad = true;
+            continue;
+        }
+        if (heads > 0 && (i + 1 >= n || nxt)) sink.plain(row, sp, sn);   // the run lies inside the tile
+        else sink.atomic(row, sp, sn);
+    }
+    if (bad) atomicOr(err, CRDT_DEV_RANGE);
+}
+
+// Cell i contributes p[idx[i]], q[idx[i]] (columns of n_src > 0 elements): the
+// gather fused behind an index-carrying sort.  No load is predicated: positions
+// are clamped into [0, n) and a refused index to element 0, so all 8 index
+// loads go out together, then all 16 gathers, and the selects follow; an index
+// at or past n_src contributes 0 and is reported.
+struct CmSrcIndexed {
+    const uint64_t *__restrict__ p, *__restrict__ q;
+    const uint32_t *__restrict__ idx;
+    uint64_t n_src;
+    __device__ __forceinline__ bool load(uint64_t tb, int wv, int lane, uint64_t n, uint64_t *xp, uint64_t *xn) const {
+        uint32_t at[RWW];
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < RWW; ++j) {                  // (the caller's tb < n: so n > 0)
+            const uint64_t i = tb + (uint64_t)(wv * RWW + j) * 64 + lane;
+            at[j] = idx[i < n ? i : n - 1];
+        }
+        uint64_t gp[RWW], gq[RWW];
+#pragma unroll
+        for (int j = 0; j < RWW; ++j) {
+            const uint32_t a = (uint64_t)at[j] < n_src ? at[j] : 0u;
+            gp[j] = p[a];
+            gq[j] = q[a];
+        }
+#pragma unroll
+        for (int j = 0; j < RWW; ++j) {
+            const uint64_t i = tb + (uint64_t)(wv * RWW + j) * 64 + lane;
+            const bool in = (uint64_t)at[j] < n_src;
+            bad |= i < n && !in;
+            xp[j] = i < n && in ? gp[j] : 0;
+            xn[j] = i < n && in ? gq[j] : 0;
+        }
+        return bad;
+    }
+};
+// the combined cells: each row's key and rep from its head cell, its sums
+template <class R>
+struct CmSinkCells {
+    const uint64_t *__restrict__ key;
+    const R *__restrict__ rep;
+    crdt_cmap out;
+    __device__ __forceinline__ void head(uint64_t i, uint64_t row) const {
+        const uint64_t k = key[i];
+        const R r = rep[i];
+        out.key[row] = k;
+        out.rep[row] = (uint32_t)r;
+    }
+    __device__ __forceinline__ void plain(uint64_t row, uint64_t sp, uint64_t sn) const {
+        out.p[row] = sp;
+        out.n[row] = sn;
+    }
+    __device__ __forceinline__ void atomic(uint64_t row, uint64_t sp, uint64_t sn) const {
+        atomicAdd((unsigned long long *)&out.p[row], (unsigned long long)sp);
+        atomicAdd((unsigned long long *)&out.n[row], (unsigned long long)sn);
+    }
+};
+// values' sums pass over the combine's heads (k_cmap_zero in front, as there)
+template <class Src, class R>
+__global__ __launch_bounds__(RB) void k_cmap_csums(Src src, const uint64_t *__restrict__ key, const R *__restrict__ rep,
+                                                   uint64_t n_max, const uint64_t *__restrict__ n_dev,
+                                                   const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ic,
+                                                   crdt_cmap out, uint32_t *__restrict__ err) {
+    __shared__ uint64_t s_tp[RNW], s_tn[RNW];
+    cmap_sums_tile(src, n_max, n_dev, bits, ic, CmSinkCells<R>{key, rep, out}, err, s_tp, s_tn);
+}
+
+// crdt_cmap_from_ops: the operations as the sort's tuples (key, ts = rep
+// widened, rep = the operation's index, tomb = 0) -- the three columns the
+// caller does not hold
+__global__ __launch_bounds__(256) void k_cmap_ops_view(const uint32_t *__restrict__ op_rep, uint64_t m,
+                                                       uint64_t *__restrict__ ts, uint32_t *__restrict__ index,
+                                                       uint8_t *__restrict__ tomb) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (uint64_t)gridDim.x * 256) {
+        ts[i] = (uint64_t)op_rep[i];
+        index[i] = (uint32_t)i;
+        tomb[i] = 0;
+    }
 }
 
 // ---------------------------------------------------------------- lookup

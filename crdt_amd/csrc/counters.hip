@@ -481,9 +481,10 @@ static int cmap_two_sided(crdt_ctx *ctx, const TileWs &w, size_t ntiles, const c
     return check_launch(ctx);
 }
 
-extern "C" int crdt_cmap_merge(crdt_ctx *ctx, const crdt_cmap *a, size_t na_max, const uint64_t *na_dev,
-                               const crdt_cmap *b, size_t nb_max, const uint64_t *nb_dev, const crdt_cmap *out,
-                               uint64_t *count_dev) {
+// the union of two states, a cell of both sides combined by Comb: the checks, the workspace, the passes
+template <class Comb>
+static int cmap_union(crdt_ctx *ctx, const crdt_cmap *a, size_t na_max, const uint64_t *na_dev, const crdt_cmap *b,
+                      size_t nb_max, const uint64_t *nb_dev, const crdt_cmap *out, uint64_t *count_dev) {
     int rc = bind(ctx);
     if (rc) return rc;
     if (!a || !b || !count_dev) return CRDT_E_INVAL;
@@ -508,7 +509,19 @@ extern "C" int crdt_cmap_merge(crdt_ctx *ctx, const crdt_cmap *a, size_t na_max,
     TileWs w;
     rc = w.reserve(ctx, ntiles, true, false, CBS);
     if (rc) return rc;
-    return cmap_two_sided<false, CmMax>(ctx, w, ntiles, *a, na_max, na_dev, *b, nb_max, nb_dev, out, count_dev);
+    return cmap_two_sided<false, Comb>(ctx, w, ntiles, *a, na_max, na_dev, *b, nb_max, nb_dev, out, count_dev);
+}
+
+extern "C" int crdt_cmap_merge(crdt_ctx *ctx, const crdt_cmap *a, size_t na_max, const uint64_t *na_dev,
+                               const crdt_cmap *b, size_t nb_max, const uint64_t *nb_dev, const crdt_cmap *out,
+                               uint64_t *count_dev) {
+    return cmap_union<CmMax>(ctx, a, na_max, na_dev, b, nb_max, nb_dev, out, count_dev);
+}
+
+extern "C" int crdt_cmap_add(crdt_ctx *ctx, const crdt_cmap *t, size_t nt_max, const uint64_t *nt_dev,
+                             const crdt_cmap *d, size_t nd_max, const uint64_t *nd_dev, const crdt_cmap *out,
+                             uint64_t *count_dev) {
+    return cmap_union<CmAdd>(ctx, t, nt_max, nt_dev, d, nd_max, nd_dev, out, count_dev);
 }
 
 extern "C" int crdt_cmap_apply(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint64_t *n_dev, uint32_t rep,
@@ -726,4 +739,124 @@ extern "C" int crdt_cmap_select(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max,
     w.scan<NoCarry<>>(ctx, n_max, n_dev, 0, nullptr, wr, count_dev);
     if (ntiles && wr) k_cmap_sel_write<<<g, kTileB, 0, s>>>(*t, n_max, n_dev, w.bits, w.ic, *out, ctx->dev_status);
     return check_launch(ctx);
+}
+
+// ---------------------------------------------------------------- combine, from_ops
+// heads -> scan -> zero -> sums over the carved tiles; R: the rep column's element; IDX: idx is always given
+// (from_ops), so that no direct sums kernel is built for that R
+template <class R, bool IDX>
+static int cmap_combine_passes(crdt_ctx *ctx, const TileWs &w, size_t ntiles, const uint64_t *key, const R *rep,
+                               const uint64_t *p, const uint64_t *q, size_t n_max, const uint64_t *n_dev,
+                               const uint32_t *idx, size_t n_src, const crdt_cmap *out, uint64_t *count_dev) {
+    const bool wr = out != nullptr;
+    const hipStream_t s = ctx->stream;
+    const unsigned g = (unsigned)ntiles;
+    if (ntiles) {
+        if (wr) k_cmap_cheads<true, R><<<g, RB, 0, s>>>(key, rep, n_max, n_dev, w.tcnt, w.bits);
+        else k_cmap_cheads<false, R><<<g, RB, 0, s>>>(key, rep, n_max, n_dev, w.tcnt, w.bits);
+    }
+    w.scan<NoCarry<>>(ctx, n_max, n_dev, 0, nullptr, wr, count_dev);
+    if (ntiles && wr) {
+        if (ntiles > 1)
+            k_cmap_zero<<<(unsigned)((ntiles + 255) / 256), 256, 0, s>>>(n_max, n_dev, w.bits, w.ic, out->p, out->n, nullptr);
+        if (IDX || idx)
+            k_cmap_csums<CmSrcIndexed, R><<<g, RB, 0, s>>>(CmSrcIndexed{p, q, idx, n_src}, key, rep, n_max, n_dev, w.bits,
+                                                           w.ic, *out, ctx->dev_status);
+        else if constexpr (!IDX)
+            k_cmap_csums<CmSrcDirect, R><<<g, RB, 0, s>>>(CmSrcDirect{p, q}, key, rep, n_max, n_dev, w.bits, w.ic, *out,
+                                                          ctx->dev_status);
+    }
+    return check_launch(ctx);
+}
+
+extern "C" int crdt_cmap_combine(crdt_ctx *ctx, const crdt_cmap *in, size_t n_max, const uint64_t *n_dev,
+                                 const uint32_t *idx_dev, size_t n_src, const crdt_cmap *out, uint64_t *count_dev) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!in || !count_dev) return CRDT_E_INVAL;
+    if (n_max >= (1ULL << 62) || (idx_dev && n_src >= (1ULL << 62))) return CRDT_E_RANGE;
+    if (n_max && (cmap_null(in) || (idx_dev && !n_src))) return CRDT_E_INVAL;
+    if (cmap_misaligned(in) || (out && cmap_misaligned(out))) return CRDT_E_INVAL;
+    if ((((uintptr_t)n_dev | (uintptr_t)count_dev) & 7) != 0 || ((uintptr_t)idx_dev & 3) != 0) return CRDT_E_INVAL;
+    const size_t ntiles = (n_max + RT - 1) / RT;
+    if (ntiles >= 0x7fffffffULL) return CRDT_E_RANGE;   // (so no byte count below wraps)
+    if (out && n_max && cmap_null(out)) return CRDT_E_INVAL;
+    {
+        const size_t nv = idx_dev ? n_src : n_max;       // elements of the p / n columns
+        CmSpan i[6], o[5];
+        int ni = 0, no = 0;
+        i[ni++] = {in->key, n_max * 8};
+        i[ni++] = {in->rep, n_max * 4};
+        i[ni++] = {in->p, nv * 8};
+        i[ni++] = {in->n, nv * 8};
+        i[ni++] = {n_dev, 8};
+        i[ni++] = {idx_dev, n_max * 4};
+        if (out) no = cmap_fields(out, n_max, o);
+        o[no++] = {count_dev, 8};
+        if (cmap_clash(o, no, i, ni)) return CRDT_E_INVAL;
+    }
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, false, false, RNW);
+    if (rc) return rc;
+    return cmap_combine_passes<uint32_t, false>(ctx, w, ntiles, in->key, in->rep, in->p, in->n, n_max, n_dev, idx_dev, n_src, out,
+                                         count_dev);
+}
+
+extern "C" int crdt_cmap_from_ops(crdt_ctx *ctx, const uint64_t *op_key_dev, const uint32_t *op_rep_dev,
+                                  const uint64_t *op_dp_dev, const uint64_t *op_dn_dev, size_t m, const crdt_cmap *out,
+                                  uint64_t *count_dev) {
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!out || !count_dev) return CRDT_E_INVAL;
+    if (m >= (1ULL << 32)) return CRDT_E_RANGE;         // the sort's limit, and the index column's width
+    if (m && (!op_key_dev || !op_rep_dev || !op_dp_dev || !op_dn_dev || cmap_null(out))) return CRDT_E_INVAL;
+    if (cmap_misaligned(out) || ((uintptr_t)op_rep_dev & 3) != 0) return CRDT_E_INVAL;
+    if ((((uintptr_t)op_key_dev | (uintptr_t)op_dp_dev | (uintptr_t)op_dn_dev | (uintptr_t)count_dev) & 7) != 0)
+        return CRDT_E_INVAL;
+    {
+        CmSpan i[4], o[5];
+        i[0] = {op_key_dev, m * 8};
+        i[1] = {op_rep_dev, m * 4};
+        i[2] = {op_dp_dev, m * 8};
+        i[3] = {op_dn_dev, m * 8};
+        int no = cmap_fields(out, m, o);
+        o[no++] = {count_dev, 8};
+        if (cmap_clash(o, no, i, 4)) return CRDT_E_INVAL;
+    }
+    // The workspace, reserved once for the whole call so that neither the sort's own reserve nor the tiles' moves
+    // it: [the sort's share | the tiles' share] from the start, both carved by their owners, and behind the larger
+    // of the two the view's three columns and the sorted tuples, which live from the sort to the last pass.
+    const size_t ntiles = (m + RT - 1) / RT;
+    const size_t b_tiles = TileWs::bytes(ntiles, false, false, RNW);
+    const size_t b_sort = m ? tuples_sort_ws_bytes(m) : 0;
+    const size_t front = Carve::round(b_sort > b_tiles ? b_sort : b_tiles);
+    const size_t b_cols = 3 * Carve::round(m * 8) + 2 * Carve::round(m * 4) + 2 * Carve::round(m) + 2048;
+    rc = ws_reserve(ctx, front + b_cols);
+    if (rc) return rc;
+    Carve x((char *)ctx->ws + front);
+    crdt_tuples view, sorted;
+    view.key = const_cast<uint64_t *>(op_key_dev);
+    view.ts = x.take<uint64_t>(m);
+    view.rep = x.take<uint32_t>(m);
+    view.tomb = x.take<uint8_t>(m);
+    sorted.key = x.take<uint64_t>(m);
+    sorted.ts = x.take<uint64_t>(m);
+    sorted.rep = x.take<uint32_t>(m);
+    sorted.tomb = x.take<uint8_t>(m);
+    if (m) {
+        k_cmap_ops_view<<<grid_for(m, 256, (unsigned)ctx->num_cus * 8), 256, 0, ctx->stream>>>(op_rep_dev, m, view.ts,
+                                                                                             view.rep, view.tomb);
+        rc = check_launch(ctx);
+        if (rc) return rc;
+        void *const ws = ctx->ws;
+        rc = crdt_tuples_sort(ctx, &view, m, &sorted);  // (synchronises once: its plan's read-back)
+        if (rc) return rc;
+        if (ctx->ws != ws) return CRDT_E_HIP;           // (never: the reserve above covers the sort's)
+    }
+    TileWs w;
+    rc = w.reserve(ctx, ntiles, false, false, RNW);
+    if (rc) return rc;
+    // sorted by (key, rep, index): the combine over the sorted key / widened rep, p and n gathered through the index
+    return cmap_combine_passes<uint64_t, true>(ctx, w, ntiles, sorted.key, sorted.ts, op_dp_dev, op_dn_dev, m, nullptr,
+                                         sorted.rep, m, out, count_dev);
 }

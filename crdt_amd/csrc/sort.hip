@@ -3259,6 +3259,15 @@ extern "C" int crdt_u64_lower_bound(crdt_ctx *ctx, const uint64_t *sorted, size_
     return check_launch(ctx);
 }
 
+// what crdt_tuples_sort reserves of the workspace, from its start on, for n tuples
+// (a caller that keeps columns of its own across the sort carves them behind this)
+size_t crdt::tuples_sort_ws_bytes(size_t n) {
+    const size_t ntiles = (n + ST - 1) / ST, ncnt = ntiles * 256;
+    const size_t b_mm = Carve::round(2 * MM_BLOCKS * sizeof(SortMinMax)), b_plan = Carve::round(sizeof(SortPlan));
+    const size_t b_cnt = Carve::round(ncnt * 4), b_tot = Carve::round(256 * 4), b_bufs = Carve::round(2 * 3 * n * 8);
+    return b_mm + b_plan + 2 * b_cnt + b_tot + b_bufs + 1024;
+}
+
 extern "C" int crdt_tuples_sort(crdt_ctx *ctx, const crdt_tuples *in, size_t n, crdt_tuples *out) {
     int rc = bind(ctx);
     if (rc) return rc;
@@ -3268,9 +3277,7 @@ extern "C" int crdt_tuples_sort(crdt_ctx *ctx, const crdt_tuples *in, size_t n, 
         return CRDT_E_INVAL;
     if (n >= (1ULL << 32)) return CRDT_E_RANGE;       // 32-bit in-tile / bucket arithmetic
     const size_t ntiles = (n + ST - 1) / ST, ncnt = ntiles * 256;
-    const size_t b_mm = Carve::round(2 * MM_BLOCKS * sizeof(SortMinMax)), b_plan = Carve::round(sizeof(SortPlan));
-    const size_t b_cnt = Carve::round(ncnt * 4), b_tot = Carve::round(256 * 4), b_bufs = Carve::round(2 * 3 * n * 8);
-    rc = ws_reserve(ctx, b_mm + b_plan + 2 * b_cnt + b_tot + b_bufs + 1024);
+    rc = ws_reserve(ctx, tuples_sort_ws_bytes(n));
     if (rc) return rc;
     Carve w(ctx->ws);
     SortMinMax *mm = w.take<SortMinMax>(2 * MM_BLOCKS);

@@ -1014,6 +1014,106 @@ class Engine:
                    _ref(out), count.data_ptr())
         return count
 
+    # -- counter-map state from unsorted increment logs: combine, add, ingest
+    #    (crdt_cmap_combine / crdt_cmap_add / crdt_cmap_from_ops)
+    def cmap_combine(self, t: CounterMap, n_dev: torch.Tensor | None = None, idx: torch.Tensor | None = None,
+                     out: CounterMap | None = None, count: torch.Tensor | None = None, trim: bool = False):
+        """Sorted cells with repeats to a state: ``t.key`` / ``t.rep``
+        ascending by (key, rep) but not strictly; out holds one cell per
+        distinct (key, rep) with p / n summed over the run mod 2^64 (a run
+        summing to 0 keeps its cell).  With ``idx`` (int32 storage of uint32,
+        one per cell of ``t.key``) cell i contributes ``t.p[idx[i]]``,
+        ``t.n[idx[i]]`` -- ``t.p`` / ``t.n`` are then columns of any length,
+        every index checked against it; one out of range contributes 0 and
+        raises CRDT_DEV_RANGE.  Returns (out, count) as :meth:`cmap_merge`
+        does, out of capacity len(t); ``n_dev`` as there.  No
+        synchronisation."""
+        out = self._out_cmap(out, len(t), "cmap_combine: out holds fewer cells than t")
+        count = self._cmap_combine(t, n_dev, idx, out, count)
+        return self._result(trim, count, out, None)
+
+    def cmap_combine_count(self, t: CounterMap, n_dev: torch.Tensor | None = None,
+                           count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(cmap_combine(t)) alone (int64[1] on the device, no
+        synchronisation): the number of distinct (key, rep)."""
+        return self._cmap_combine(t, n_dev, None, None, count)
+
+    def _cmap_combine(self, t: CounterMap, n_dev, idx, out, count) -> torch.Tensor:
+        count = self._count(count)
+        self._check(count, n_dev, itemsize=8)
+        self._check(idx, itemsize=4)
+        n = len(t)
+        if t.rep.numel() != n or t.p.numel() != t.n.numel():
+            raise ValueError("cmap_combine: one rep per key, and p and n of one length")
+        if idx is None and out is not None and t.p.numel() != n:   # (the count alone reads neither)
+            raise ValueError("cmap_combine: without idx, one p and one n per key")
+        if idx is not None and idx.numel() != n:
+            raise ValueError("cmap_combine: one index per cell")
+        self._check_cmap(t, out)
+        self._call("crdt_cmap_combine", _ref(t), n, _ptr(n_dev), _ptr(idx), t.p.numel() if idx is not None else 0,
+                   _ref(out), count.data_ptr())
+        return count
+
+    def cmap_add(self, t: CounterMap, d: CounterMap, n_t_dev: torch.Tensor | None = None,
+                 n_d_dev: torch.Tensor | None = None, out: CounterMap | None = None,
+                 count: torch.Tensor | None = None, trim: bool = False):
+        """The additive join of the state ``t`` and the batch ``d`` (both
+        strictly ascending): the union of the cells, a cell held by both with
+        (p_t + p_d, n_t + n_d) mod 2^64, a cell of ``d`` alone created with
+        d's values.  ``cmap_apply`` with many replicas in one pass.  NOT
+        idempotent: each batch is delivered once, which is the caller's to
+        ensure.  Returns (out, count) as :meth:`cmap_merge` does, out of
+        capacity len(t) + len(d); ``n_t_dev`` / ``n_d_dev`` as its lengths."""
+        out = self._out_cmap(out, len(t) + len(d), "cmap_add: out holds fewer cells than len(t) + len(d)")
+        count = self._cmap_add(t, d, n_t_dev, n_d_dev, out, count)
+        return self._result(trim, count, out, None)
+
+    def cmap_add_count(self, t: CounterMap, d: CounterMap, n_t_dev: torch.Tensor | None = None,
+                       n_d_dev: torch.Tensor | None = None, count: torch.Tensor | None = None) -> torch.Tensor:
+        """len(cmap_add(t, d)) alone (int64[1] on the device, no
+        synchronisation): nothing is written but the count."""
+        return self._cmap_add(t, d, n_t_dev, n_d_dev, None, count)
+
+    def _cmap_add(self, t: CounterMap, d: CounterMap, n_t_dev, n_d_dev, out, count) -> torch.Tensor:
+        count = self._count(count)
+        self._check(count, n_t_dev, n_d_dev, itemsize=8)
+        self._check_cmap(t, d, out)
+        self._call("crdt_cmap_add", _ref(t), len(t), _ptr(n_t_dev), _ref(d), len(d), _ptr(n_d_dev), _ref(out),
+                   count.data_ptr())
+        return count
+
+    def cmap_from_ops(self, op_keys: torch.Tensor, op_reps: torch.Tensor, op_dp: torch.Tensor, op_dn: torch.Tensor,
+                      out: CounterMap | None = None, count: torch.Tensor | None = None, trim: bool = False):
+        """An increment log to a state: operations (op_keys[i], op_reps[i],
+        +op_dp[i], -op_dn[i]) in any order, repeats and any mix of replicas
+        (int64 storage of uint64; ``op_reps`` int32 storage of uint32).  Cell
+        (k, r) of the result holds the sums mod 2^64 over the operations of
+        that key and replica; the operations' order does not matter.  Returns
+        (out, count) as :meth:`cmap_merge` does, out of capacity
+        len(op_keys) < 2^32.  Synchronises once (the device sort's plan)."""
+        m = op_keys.numel()
+        out = self._out_cmap(out, m, "cmap_from_ops: out holds fewer cells than there are operations")
+        count = self._count(count)
+        self._check(count, op_keys, op_dp, op_dn, itemsize=8)
+        self._check(op_reps, itemsize=4)
+        if op_reps.numel() != m or op_dp.numel() != m or op_dn.numel() != m:
+            raise ValueError("cmap_from_ops: one rep, one dp and one dn per operation key")
+        self._check_cmap(out)
+        self._call("crdt_cmap_from_ops", _ptr(op_keys) if m else None, _ptr(op_reps) if m else None,
+                   _ptr(op_dp) if m else None, _ptr(op_dn) if m else None, m, _ref(out), count.data_ptr())
+        return self._result(trim, count, out, None)
+
+    def cmap_ingest(self, t: CounterMap, op_keys: torch.Tensor, op_reps: torch.Tensor, op_dp: torch.Tensor,
+                    op_dn: torch.Tensor, n_t_dev: torch.Tensor | None = None, out: CounterMap | None = None,
+                    count: torch.Tensor | None = None, trim: bool = False):
+        """The log applied to the state ``t``: :meth:`cmap_from_ops`, then
+        :meth:`cmap_add` chained off its device count with no further
+        read-back.  Returns (out, count), out of capacity len(t) +
+        len(op_keys).  Each log is ingested once (see :meth:`cmap_add`)."""
+        batch, nb = self.cmap_from_ops(op_keys, op_reps, op_dp, op_dn)
+        return self.cmap_add(t, batch.slice(op_keys.numel()), n_t_dev=n_t_dev, n_d_dev=nb, out=out, count=count,
+                             trim=trim)
+
     # -- the causal merge restricted to the key ranges whose digests differ
     #    (crdt_orset_merge_causal_ranges)
     def causal_merge_ranges(self, a: TupleSet, ctx_a: torch.Tensor | None, b: TupleSet, ctx_b: torch.Tensor | None,

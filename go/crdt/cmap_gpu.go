@@ -101,3 +101,43 @@ func CMapSelect(t *C.crdt_cmap, nMax int, nDev, splittersDev *C.uint64_t, m int,
 	}
 	return status(C.crdt_cmap_select(gpuCtx, t, C.size_t(nMax), nDev, splittersDev, C.size_t(m), flagsDev, out, countDev))
 }
+
+// CMapCombine: sorted cells with repeats -- in ascending by (key, rep) but not
+// strictly -- into one cell per distinct (key, rep), p and n summed over the
+// run mod 2^64 (capacity nMax; nil out: the count alone).  With idxDev (nMax
+// uint32 values) cell i contributes in.p[idx[i]], in.n[idx[i]], columns of
+// nSrc elements; an index out of range contributes 0 and raises
+// CRDT_DEV_RANGE.  The per-key sum of the replay (main.go:87-96) over a sorted
+// log.  Enqueued.
+func CMapCombine(in *C.crdt_cmap, nMax int, nDev *C.uint64_t, idxDev *C.uint32_t, nSrc int, out *C.crdt_cmap,
+	countDev *C.uint64_t) error {
+	if in == nil || countDev == nil || nMax < 0 || nSrc < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_combine(gpuCtx, in, C.size_t(nMax), nDev, idxDev, C.size_t(nSrc), out, countDev))
+}
+
+// CMapAdd: the additive join of the state t and the batch d (both strictly
+// ascending) -- the union of the cells, a cell of both with (p_t + p_d, n_t +
+// n_d), a cell of d alone created with d's values -- into out (capacity ntMax +
+// ndMax; nil: the count alone).  CMapApply for many replicas in one pass.  Not
+// idempotent: each batch is delivered once.  Enqueued.
+func CMapAdd(t *C.crdt_cmap, ntMax int, ntDev *C.uint64_t, d *C.crdt_cmap, ndMax int, ndDev *C.uint64_t,
+	out *C.crdt_cmap, countDev *C.uint64_t) error {
+	if t == nil || d == nil || countDev == nil || ntMax < 0 || ndMax < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_add(gpuCtx, t, C.size_t(ntMax), ntDev, d, C.size_t(ndMax), ndDev, out, countDev))
+}
+
+// CMapFromOps: m operations (opKey[i], opRep[i], +opDp[i], -opDn[i]) in any
+// order, with repeats and any mix of replicas -- the log the replay walks
+// (main.go:75-98) -- into the state whose cell (k, r) holds their sums (out of
+// capacity m).  Synchronises once, for the device sort's plan.
+func CMapFromOps(opKeyDev *C.uint64_t, opRepDev *C.uint32_t, opDpDev, opDnDev *C.uint64_t, m int, out *C.crdt_cmap,
+	countDev *C.uint64_t) error {
+	if out == nil || countDev == nil || m < 0 {
+		return status(C.CRDT_E_INVAL)
+	}
+	return status(C.crdt_cmap_from_ops(gpuCtx, opKeyDev, opRepDev, opDpDev, opDnDev, C.size_t(m), out, countDev))
+}

@@ -220,6 +220,60 @@ int crdt_cmap_select(crdt_ctx *ctx, const crdt_cmap *t, size_t n_max, const uint
                      const uint64_t *splitters_dev, size_t m, const uint8_t *flags_dev, /* m + 1 */
                      const crdt_cmap *out, uint64_t *count_dev);                /* out >= n_max cells; NULL: count alone */
 
+/* Counter-map state from increment logs: the per-key sum of the reference's
+ * replay (main.go:87-96) over a log in any order.  crdt_cmap_apply takes one
+ * replica's batch, strictly ascending, each key once; the three calls below
+ * take what a log, a Diff or a gossip body really is -- cells (key, rep, p,
+ * n) with repeats and many replicas interleaved.  All sums are modulo 2^64,
+ * all orders unsigned; lengths, refusals, alignment and synchronisation are
+ * the family's (above) unless said otherwise.
+ *
+ * crdt_cmap_combine: `in` ascending by (key, rep) but NOT strictly -- runs of
+ * equal (key, rep) of any length, a whole input that is one run included.
+ * out = one cell per distinct (key, rep), ascending, p = the sum of p and n =
+ * the sum of n over the run: a valid state.  A run whose sums are 0 still
+ * yields its cell (crdt_cmap_apply's rule).  idx_dev == NULL: position i
+ * contributes in->p[i], in->n[i].  idx_dev != NULL (n_max uint32 values,
+ * 4-byte aligned): position i contributes in->p[idx[i]], in->n[idx[i]], in->p
+ * / in->n being columns of n_src elements -- the gather fused behind an
+ * index-carrying sort.  Every idx[i] is checked against n_src before the
+ * load; one at or past it contributes 0 and raises CRDT_DEV_RANGE, every
+ * other cell is still exact.  out holds >= n_max cells and overlaps nothing;
+ * out == NULL: the count alone.  *n_dev > n_max touches no cell, stores a
+ * count of ~0 and raises CRDT_DEV_RANGE; n_max == 0 stores count 0.  Never
+ * synchronises, workspace from the context only, capturable after
+ * crdt_ctx_reserve.  For an input that is not ascending the result is
+ * unspecified, but no access leaves the given lengths and count <= n.
+ * CRDT_E_INVAL beyond the family's: idx_dev with n_max != 0 and n_src == 0. */
+int crdt_cmap_combine(crdt_ctx *ctx, const crdt_cmap *in, size_t n_max, const uint64_t *n_dev,
+                      const uint32_t *idx_dev, size_t n_src,
+                      const crdt_cmap *out, uint64_t *count_dev);
+/* The additive join of two states (both strictly ascending): the union of the
+ * cells; a cell held by both sides gets (p_t + p_d, n_t + n_d); a cell held by
+ * d alone is created with d's values, zeros included.  crdt_cmap_apply(t, rep,
+ * keys, dp, dn) equals crdt_cmap_add(t, {keys, rep ..., dp, dn}) bit for bit.
+ * NOT idempotent, unlike crdt_cmap_merge: d is a batch of increments, and each
+ * batch must be delivered exactly once -- the caller's obligation, as for any
+ * op-based input.  out holds >= nt_max + nd_max cells; out == NULL: the count
+ * alone. */
+int crdt_cmap_add(crdt_ctx *ctx, const crdt_cmap *t, size_t nt_max, const uint64_t *nt_dev,
+                  const crdt_cmap *d, size_t nd_max, const uint64_t *nd_dev,
+                  const crdt_cmap *out, uint64_t *count_dev);
+/* m operations (op_key[i], op_rep[i], +op_dp[i], -op_dn[i]) in ANY order, with
+ * repeats and any mix of replicas: out = the state whose cell (k, r) holds the
+ * sums of dp / dn over the operations with that key and replica, whatever the
+ * operations' order.  out (not NULL) holds >= m cells.  The operations are
+ * ordered by crdt_tuples_sort's machinery, as tuples (key, ts = rep widened,
+ * rep = operation index, tomb = 0), then combined with the sorted index column
+ * as idx over op_dp / op_dn.  SYNCHRONISES ONCE, for the sort's plan
+ * read-back: the one call of the family that is not capturable.  CRDT_E_RANGE:
+ * m >= 2^32.  CRDT_E_INVAL: a NULL out or count_dev, NULL operation columns or
+ * out fields with m != 0, misalignment, any output overlapping an input or
+ * another output. */
+int crdt_cmap_from_ops(crdt_ctx *ctx, const uint64_t *op_key_dev, const uint32_t *op_rep_dev,
+                       const uint64_t *op_dp_dev, const uint64_t *op_dn_dev, size_t m,
+                       const crdt_cmap *out, uint64_t *count_dev);
+
 /* ------------------------------------------- streaming peaks
  * Measurement utilities, no reference counterpart: the bench reports every
  * kernel's fraction of a self-measured copy-kernel peak beside the spec peak.
